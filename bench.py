@@ -2,7 +2,7 @@
 """Benchmark of the Sopro synthesize hot path on MI355X (BASELINE.json metric: audio-seconds per
 wall-second, plus p50 time-to-first-audio of stream()).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path over one batch of synthetic input: 32 utterances x 200 frames
 (BASELINE.json configs[1]) through conditioning -> AR loop (hipGraph replay) -> NAR refinement -> Mimi
@@ -11,7 +11,11 @@ region starts.  N > 1 (launched by torch.distributed.run, one rank per GPU) is w
 synthesises its own 32 utterances, there is no data-path collective; the timed region is bracketed by a
 barrier + device sync on both sides and the MAX over ranks is reported.
 
-One JSON line is printed by rank 0.  Extra objects on it:
+A plain run sets up, warms up, times the K steps and prints one JSON line (rank 0): the headline, `ms_per_step`, `config`
+and the phase times of the timed region.  --dump-outputs DIR also writes the waveforms of the last timed step (rank 0) to
+DIR/waveforms.npy (see dump_outputs).  Everything else runs with --full only: the p50 time-to-first-audio of stream()
+(config.second_metric), the extra legs (config.legs) and the objects below; the full record then goes to bench_full.json
+next to bench.py and to stderr.
   roofline     -- the dominant kernel family of the step BY SUMMED HIP-EVENT TIME over every instrumented family, the AR
                   frame graph included (it is the largest: the 23-launch per-frame graph of the autoregressive loop):
                   algorithmic bytes (HBM bound) or flops (MFMA bound) per launch / average launch time; the other
@@ -343,6 +347,21 @@ def leg_main(name: str, args, device: str) -> dict:
 
 LINE_LIMIT = 8192  # the driver parses the last stdout line from a bounded buffer (round 5: a 21 kB line came back as parsed = null)
 FULL_RECORD = "bench_full.json"
+DUMP_LIMIT = 60_000_000  # bytes of --dump-outputs in all (under 64 MB with the .npy header)
+
+
+def dump_outputs(out_dir: str, wavs) -> None:
+    """--dump-outputs: the waveforms of the last timed step, what synthesize_batch / PipelinedSynthesizer.run hand back (one
+    [1, 1, N] tensor per utterance), as DIR/waveforms.npy: float32 [utterances, N].  Every timed step runs the same seeded job
+    on the same seeded inputs, so two builds can be compared sample for sample.  Above DUMP_LIMIT bytes only a fixed sample of
+    sample positions (seed 0, sorted, the same in every row) is written."""
+    a = torch.stack([o.reshape(-1) for o in wavs]).float().cpu().numpy()
+    if a.nbytes > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (a.shape[0] * a.itemsize)
+        a = np.ascontiguousarray(a[:, np.sort(np.random.default_rng(0).choice(a.shape[1], keep, replace=False))])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "waveforms.npy"), a)
+    log(f"wrote {os.path.join(out_dir, 'waveforms.npy')}: {a.dtype} {list(a.shape)}")
 
 
 def _pick(d, keys):
@@ -352,7 +371,7 @@ def _pick(d, keys):
 def compact_line(full: dict) -> dict:
     """The ONE stdout line: headline keys, `config` (second metric + compact legs), `roofline` (primary family + the batch-1 frame),
     `roofline_more` reduced to the figures a reader checks, `cpu_baseline`, `parity`.  Everything else (per-kernel tables, prose,
-    profile stamps, full legs) is in FULL_RECORD next to bench.py, in gpurun_out/ when that exists, and on stderr."""
+    profile stamps, full legs) is in FULL_RECORD next to bench.py and on stderr."""
     roof_keys = ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_ratio", "launches", "avg_launch_us", "ms_per_step",
                  "concurrent_phases", "wall_ms_per_step", "algorithmic_bytes_per_launch", "algorithmic_flops_per_launch", "rows_per_launch",
                  "cu_share", "frac_of_pass_ceiling", "mfma_busy_pmc", "avg_launch_us_rocprof", "phase", "frac_reading")
@@ -398,18 +417,21 @@ def compact_line(full: dict) -> dict:
     return out
 
 
-def emit(full: dict, root: str) -> str:
-    """Write the full record to a side file (+ stderr) and print the compact line (< LINE_LIMIT bytes) as the last stdout line."""
-    blob = json.dumps(full)
-    for d in (root, os.path.join(root, "gpurun_out")):
-        if os.path.isdir(d):
-            try:
-                with open(os.path.join(d, FULL_RECORD), "w") as fh:
-                    fh.write(blob + "\n")
-            except OSError as e:  # a read-only tree must not void the measurement
-                log(f"could not write {FULL_RECORD} in {d}: {e!r}")
-    print("[bench full record] " + blob, file=sys.stderr, flush=True)
-    text = json.dumps(compact_line(full), separators=(",", ":"))
+def emit(full: dict, root: str, record: bool = True) -> str:
+    """Print the compact line (< LINE_LIMIT bytes) as the last stdout line; with `record` (--full) write the full record to a
+    side file next to bench.py (+ stderr) first."""
+    line = compact_line(full)
+    if record:
+        blob = json.dumps(full)
+        try:
+            with open(os.path.join(root, FULL_RECORD), "w") as fh:
+                fh.write(blob + "\n")
+        except OSError as e:  # a read-only tree must not void the measurement
+            log(f"could not write {FULL_RECORD} in {root}: {e!r}")
+        print("[bench full record] " + blob, file=sys.stderr, flush=True)
+    else:
+        del line["full_record"]
+    text = json.dumps(line, separators=(",", ":"))
     assert len(text) < LINE_LIMIT, f"bench line is {len(text)} bytes (limit {LINE_LIMIT}): trim compact_line()"
     print(text, flush=True)
     return text
@@ -428,6 +450,9 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel rooflines, parity checks, time-to-first-audio, "
+                    "CPU baseline and the extra legs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the waveforms of the last timed step to DIR/waveforms.npy (float32)")
     ap.add_argument("--profile-steps", type=int, default=4, help="instrumented repeat of the steps for the per-kernel roofline (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-utts", type=int, default=6)
@@ -444,7 +469,7 @@ def main() -> None:
     ap.add_argument("--coalesce", default="auto", help="consecutive batches the pipeline generates / refines / decodes as ONE pass (per-utterance results are unchanged): "
                     "an integer, or 'auto' = sized by the queue depth (2 per pass for short queues, 4 from 4 queued batches per lane)")
     ap.add_argument("--voices", type=int, default=-1, help="distinct reference voices per batch (default: one per utterance, SURVEY 8d; 1 = one shared voice)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra legs of the default run (one shared voice, 32x400 / 1x400 frames, bf16 mode)")
+    ap.add_argument("--no-legs", action="store_true", help="skip the extra legs of a --full run (one shared voice, 32x400 / 1x400 frames, bf16 mode)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--leg", type=str, default="", help=argparse.SUPPRESS)  # child process of the default run: one extra leg (see LEGS)
     ap.add_argument("--parity-tokens", type=str, default="", help=argparse.SUPPRESS)
@@ -589,6 +614,8 @@ def main() -> None:
     dt = time.perf_counter() - t0
     host_cpu = time.process_time() - c0
     log(f"timed region done: {dt:.3f} s for {args.steps} steps; peak device memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+    if args.dump_outputs and rank == 0 and kept:
+        dump_outputs(args.dump_outputs, kept[-1])
     if os.environ.get("SOPRO_BENCH_MEMCENSUS", "0") == "1":  # developer: who holds the device memory (stderr)
         lanes_ = pipe.lanes if pipe is not None else [tts]
         for li, ln in enumerate(lanes_):
@@ -617,27 +644,30 @@ def main() -> None:
     ar_log, hip.phase_log = hip.phase_log, None
     ar_frames = sum(n for n, _b, _e0, _e1 in ar_log)
     ar_ms = sum(e0.elapsed_time(e1) for _n, _b, e0, e1 in ar_log)
-    steps_identical = bool(len(kept) == 2 and all(torch.equal(a, b) for a, b in zip(kept[0], kept[1])))
-    finite = bool(kept and all(bool(torch.isfinite(o).all()) for o in kept[-1]))
-    # content hash of this rank's last step (PCM16 of every utterance): N ranks must reproduce what N single-GPU runs give
-    import hashlib
+    steps_identical = finite = rank_hashes = None
+    if args.full:
+        steps_identical = bool(len(kept) == 2 and all(torch.equal(a, b) for a, b in zip(kept[0], kept[1])))
+        finite = bool(kept and all(bool(torch.isfinite(o).all()) for o in kept[-1]))
+        # content hash of this rank's last step (PCM16 of every utterance): N ranks must reproduce what N single-GPU runs give
+        import hashlib
 
-    from sopro_amd.wire import float_to_pcm16le
+        from sopro_amd.wire import float_to_pcm16le
 
-    hsh = hashlib.sha256()
-    for o in (kept[-1] if kept else []):
-        hsh.update(float_to_pcm16le(o.reshape(1, -1)))
-    rank_hashes = [hsh.hexdigest()[:16]]
-    if world > 1:
-        allh = [None] * world
-        dist.all_gather_object(allh, rank_hashes[0])
-        rank_hashes = allh
+        hsh = hashlib.sha256()
+        for o in (kept[-1] if kept else []):
+            hsh.update(float_to_pcm16le(o.reshape(1, -1)))
+        rank_hashes = [hsh.hexdigest()[:16]]
+        if world > 1:
+            allh = [None] * world
+            dist.all_gather_object(allh, rank_hashes[0])
+            rank_hashes = allh
     kept.clear()
     host_cpu_ranks = [round(host_cpu / args.steps, 4)]
     if world > 1:
-        allc = [None] * world
-        dist.all_gather_object(allc, host_cpu_ranks[0])
-        host_cpu_ranks = allc
+        if args.full:
+            allc = [None] * world
+            dist.all_gather_object(allc, host_cpu_ranks[0])
+            host_cpu_ranks = allc
         t = torch.tensor([dt], device="cpu" if share_gpu else device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
@@ -646,7 +676,7 @@ def main() -> None:
     # are issued eagerly here so that their launches are visible one by one; the timed region above is not instrumented.
     prof = hip.Profiler()
     phases_prof: dict = {}  # phase times (device events) of the instrumented repeat itself
-    nprof = max(0, min(args.profile_steps, args.steps))
+    nprof = max(0, min(args.profile_steps, args.steps)) if args.full else 0
     if nprof > 0:
         hip.set_profiler(prof)
         run_steps(nprof, phases_prof)
@@ -671,7 +701,7 @@ def main() -> None:
                 scale_of[ph] = (phases[ph] / args.steps) / (phases_prof[ph] / nprof)
         tot_t, tot_p = sum(phases.get(k, 0.0) for k in bulk) / args.steps, sum(phases_prof.get(k, 0.0) for k in bulk) / nprof
         scale_of[None] = (tot_t / tot_p) if tot_t > 0 and tot_p > 0 else 1.0
-    rocf = rocprof_family_table()
+    rocf = rocprof_family_table() if args.full else {}
     for k, v in fam.items():
         if k == "ar_step_graph":
             continue
@@ -686,7 +716,7 @@ def main() -> None:
             # time is then the committed rocprof average of its launches, and the entry says so
             v["ms"] = rocf["families"][k] * 1e-3 * max(1, v["launches"])
             v["phase_scale"], v["timing"] = None, "rocprof average (instrumented phase / timed phase = %.3g: unrepresentative repeat)" % sc
-    pmc_d, busy_d, ark = latest_profile("pmc_summary.json"), latest_profile("pmc_mfma_busy.json"), latest_profile("ar_kernels.json")
+    pmc_d, busy_d, ark = (latest_profile("pmc_summary.json"), latest_profile("pmc_mfma_busy.json"), latest_profile("ar_kernels.json")) if args.full else ({}, {}, {})
     pmc, busy = pmc_d.get("families", {}), busy_d.get("families", {})
     stamp_of = lambda d: profile_stamp(os.path.join(ROOT, d["source"])) if d.get("source") else None  # noqa: E731
     share = (256 - args.ar_cus * (1 if args.ar_shared else args.ar_parts)) / 256.0 if (args.lanes > 1 and args.ar_cus > 0) else 1.0  # CUs of the bulk partition
@@ -867,7 +897,7 @@ def main() -> None:
 
     # ---- one greedy batch of the same shape for the parity leg (row 0 goes to the oracle in the CPU child below)
     parity_path = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import tempfile
 
         log("greedy parity batch")
@@ -878,7 +908,7 @@ def main() -> None:
 
     # ---- p50 time-to-first-audio of stream(), batch 1 (BASELINE.json configs[2]); outside the timed steps
     ttfa = None
-    if rank == 0 and args.ttfa_runs > 0:
+    if args.full and rank == 0 and args.ttfa_runs > 0:
         log("ttfa")
         lat = []
         TTFA_WARM = 5
@@ -902,7 +932,7 @@ def main() -> None:
     # released first.
     legs = None
     default_shape = (BATCH, FRAMES) == (32, 200) and args.precision == "f32"
-    if rank == 0 and world == 1 and default_shape and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and default_shape and not args.no_legs:
         import subprocess
 
         legs = {}
@@ -926,7 +956,7 @@ def main() -> None:
                 legs[name] = {"error": repr(e)}
 
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import subprocess
 
         log("cpu baseline + oracle parity (child process, <= 180 s)")
@@ -948,12 +978,13 @@ def main() -> None:
         except Exception as e:  # noqa: BLE001  (a missing baseline must not void the GPU measurement)
             log(f"cpu baseline failed: {e!r}")
             cpu = None
-    parity = dict(parity or {}, timed_steps_identical=steps_identical, timed_outputs_finite=finite, rank_output_sha16=rank_hashes,
-                  f16_range_fallbacks=range_fallbacks,
-                  how="all timed steps run one seeded job: first vs last step compared bit for bit; oracle leg: row 0 of a greedy batch of "
-                      "the same shape vs oracle/sopro_oracle.py (codebook 0 exact; refined tokens exact or audited near-ties < 1e-4)")
-    if args.precision != "f32":  # the bf16 mode is a throughput mode with its own quality numbers (tests/test_gpu_bf16_mode.py), not a parity mode
-        parity["mode"] = f"{args.precision}: not a parity mode - 'ok' compares with the fp32 oracle and is expected to be false"
+    if args.full:
+        parity = dict(parity or {}, timed_steps_identical=steps_identical, timed_outputs_finite=finite, rank_output_sha16=rank_hashes,
+                      f16_range_fallbacks=range_fallbacks,
+                      how="all timed steps run one seeded job: first vs last step compared bit for bit; oracle leg: row 0 of a greedy batch of "
+                          "the same shape vs oracle/sopro_oracle.py (codebook 0 exact; refined tokens exact or audited near-ties < 1e-4)")
+        if args.precision != "f32":  # the bf16 mode is a throughput mode with its own quality numbers (tests/test_gpu_bf16_mode.py), not a parity mode
+            parity["mode"] = f"{args.precision}: not a parity mode - 'ok' compares with the fp32 oracle and is expected to be false"
 
     if rank == 0:
         audio_sec = world * args.steps * BATCH * FRAMES * FRAME_SEC
@@ -1012,7 +1043,7 @@ def main() -> None:
                          "only - torchaudio is not in the image to generate a fixture from"],
             "roofline": roof, "roofline_more": roof_more, "cpu_baseline": cpu, "parity": parity,
         }
-        emit(line, ROOT)
+        emit(line, ROOT, record=args.full)
     if world > 1:
         dist.destroy_process_group()
 

@@ -1,24 +1,34 @@
 """bench.py's multi-rank path on ONE GPU (SOPRO_BENCH_SHARE_GPU=1: every rank on device 0, gloo for the barrier / MAX):
 the launch path the driver uses for N > 1 (torch.distributed.run, one rank per GPU), the per-rank input sharding and the
-rank-0 JSON line.  Each rank's output must be what a single-GPU run on that rank's inputs produces."""
+rank-0 JSON line.  Each rank's output must be what a single-GPU run on that rank's inputs produces.  These runs take --full
+(parity, full record); the plain run and --dump-outputs are checked against one of them."""
+import hashlib
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT
+from sopro_amd.wire import float_to_pcm16le
 
 pytestmark = pytest.mark.gpu
 SMALL = ["--steps", "2", "--warmup", "1", "--batch", "4", "--frames", "24", "--lanes", "1", "--profile-steps", "0", "--ttfa-runs", "0",
          "--no-cpu-baseline"]
 
 
-def _bench(extra, env=None):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *extra], capture_output=True, text=True, timeout=900,
+def _run(args, env=None):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *args], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, **(env or {})), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
+    return r
+
+
+def _bench(extra, env=None):
+    r = _run(["--full", *extra], env)
     last = r.stdout.strip().splitlines()[-1]
     assert len(last) < 8192, len(last)  # the driver parses the last stdout line from a bounded buffer (round 5: 21 kB -> parsed = null)
     line = json.loads(last)
@@ -67,3 +77,21 @@ def test_eight_ranks_on_the_shared_gpu():
     assert max(cpu) < 1.0 * eight["ms_per_step"] * 1e-3 + 0.02
     assert abs(eight["value"] * eight["ms_per_step"] - 8 * 4 * 24 * 0.08 * 1e3) < 1e-3 * eight["value"] * eight["ms_per_step"]
     assert eight["host_threads"]["torch_intra_op"] == 1
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only (no parity, rooflines, baseline or full record), and --dump-outputs
+    writes the last timed step's waveforms: float32 [batch, frames x 1920], the same samples a --full run hashes."""
+    r = _run(["--gpus", "1", "--dump-outputs", str(tmp_path)])
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "audio_seconds_per_second" and line["steps"] == 2 and line["dtype"] == "f32" and line["higher_is_better"]
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 4 * 24 * 0.08 * 1e3) < 1e-3 * line["value"] * line["ms_per_step"]
+    assert line["roofline"] is None and line["parity"] is None and line["cpu_baseline"] is None and "full_record" not in line
+    assert not any(ln.startswith("[bench full record] ") for ln in r.stderr.splitlines())
+    wav = np.load(tmp_path / "waveforms.npy")
+    assert wav.dtype == np.float32 and wav.shape == (4, 24 * 1920) and np.isfinite(wav).all()
+    hsh = hashlib.sha256()
+    for row in wav:
+        hsh.update(float_to_pcm16le(torch.from_numpy(row).reshape(1, -1)))
+    full = _bench(["--gpus", "1"])
+    assert full["parity"]["rank_output_sha16"] == [hsh.hexdigest()[:16]]

@@ -3,7 +3,6 @@
 (reference: src/sopro/model.py:419-451).  CPU parts run everywhere; building the engine needs the GPU."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from sopro_amd.weights import (load_cfg_from_safetensors, load_safetensors, save
                                check_against_spec, synth_mimi_weights, synth_sopro_weights)
 
 VOCAB = 64
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_checkpoint_round_trip_keeps_config_and_tensors(tmp_path):
@@ -44,23 +44,30 @@ def test_cfg_metadata_is_a_key_intersection_like_the_reference(tmp_path):
         load_cfg_from_safetensors(q)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/sopro"), reason="the reference checkout exists in the build container only")
 def test_the_reference_reader_accepts_our_checkpoint(tmp_path):
-    """Our writer -> the reference's own load_cfg_from_safetensors / load_state_dict_from_safetensors (hub.py:30-52)."""
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, "/root/reference/src")
-    try:
-        from sopro.hub import load_cfg_from_safetensors as ref_cfg, load_state_dict_from_safetensors as ref_sd
-    finally:
-        sys.path.remove("/root/reference/src")
+    """Our writer -> the reference's own load_cfg_from_safetensors / load_state_dict_from_safetensors (hub.py:30-52), as
+    recorded in tests/golden/reference_reader.json (make_golden_reference_reader.py, same inputs): the reference keeps the
+    keys of __metadata__["cfg"] that are fields of its config and reads the tensors with safetensors' load_file.  Our file
+    must carry every one of those fields with the value the reference read, and exactly the tensors it returned."""
+    import hashlib
+    import struct
+
+    from safetensors.torch import load_file
+
+    rec = json.load(open(os.path.join(GOLDEN, "reference_reader.json")))
     cfg = SoproTTSConfig(style_strength=1.25)
     w = synth_sopro_weights(cfg, VOCAB, 4)
     p = str(tmp_path / "model.safetensors")
     save_sopro_checkpoint(p, w, cfg)
-    rc = ref_cfg(p)
-    assert float(rc.style_strength) == 1.25 and tuple(rc.ar_dilation_cycle) == tuple(cfg.ar_dilation_cycle)
-    sd = ref_sd(p)
-    assert set(sd) == set(w) and torch.equal(sd["ar.head.weight"], torch.from_numpy(w["ar.head.weight"]))
+    with open(p, "rb") as f:  # safetensors layout: 8-byte little-endian header length, then the JSON header
+        meta = json.loads(f.read(struct.unpack("<Q", f.read(8))[0]))["__metadata__"]
+    got = json.loads(meta["cfg"])
+    assert {k: got[k] for k in rec["cfg"] if k in got} == rec["cfg"]
+    assert rec["cfg"]["style_strength"] == 1.25 and tuple(rec["cfg"]["ar_dilation_cycle"]) == tuple(cfg.ar_dilation_cycle)
+    sd = load_file(p)
+    assert set(sd) == set(w) and {k: {"dtype": str(v.dtype), "shape": list(v.shape)} for k, v in sd.items()} == rec["tensors"]
+    assert torch.equal(sd["ar.head.weight"], torch.from_numpy(w["ar.head.weight"]))
+    assert hashlib.sha256(sd["ar.head.weight"].contiguous().numpy().tobytes()).hexdigest() == rec["ar_head_weight_sha256"]
 
 
 def test_half_precision_checkpoints_load_as_float32(tmp_path):

@@ -47,9 +47,9 @@ fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
   cd $R
   # (round 6: stdout = the compact line the driver parses, < 8 kB; the full record is bench_full.json next to bench.py, kept per run)
-  timeout 500 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; cp bench_full.json $O/bench_line_full.json
-  timeout 500 python bench.py > $O/bench_line_default.json 2> $O/bench_line_default.err; cp bench_full.json $O/bench_line_default_full.json
-  timeout 300 python bench.py --steps 20 --warmup 5 --precision bf16 > $O/bench_line_bf16.json 2> $O/bench_line_bf16.err; cp bench_full.json $O/bench_line_bf16_full.json
+  timeout 500 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; cp bench_full.json $O/bench_line_full.json
+  timeout 500 python bench.py --full > $O/bench_line_default.json 2> $O/bench_line_default.err; cp bench_full.json $O/bench_line_default_full.json
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --precision bf16 > $O/bench_line_bf16.json 2> $O/bench_line_bf16.err; cp bench_full.json $O/bench_line_bf16_full.json
   Q="--no-cpu-baseline --ttfa-runs 0 --profile-steps 0"
   ( echo '{"runs": [';
     timeout 300 python bench.py --frames 400 --steps 12 --warmup 4 $Q 2>/dev/null | tail -1; echo ',';

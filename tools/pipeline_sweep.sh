@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-.}; mkdir -p gpurun_out
 run() {  # name, env..., -- args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  out=$(env "${envs[@]}" timeout 240 python bench.py --steps 12 --warmup 4 --no-cpu-baseline --ttfa-runs 0 --profile-steps 2 "$@" 2>/dev/null | tail -1)
+  out=$(env "${envs[@]}" timeout 240 python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --ttfa-runs 0 --profile-steps 2 "$@" 2>/dev/null | tail -1)
   echo "$name $(echo "$out" | python -c 'import sys,json
 try:
     d=json.loads(sys.stdin.read()); r=[d["roofline"]]+d["roofline_more"]; ar=[e for e in r if e["kernel"].startswith("AR frame")]

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SOPRO_ABI_VERSION 41
+#define SOPRO_ABI_VERSION 42
 
 /* ---- error handling / introspection ------------------------------------------------ */
 const char* sopro_last_error(void);
@@ -784,6 +784,35 @@ int sopro_mimi_stream_trim(sopro_mimi_stream_state* st, int32_t n);
 /* workspace: sopro_mimi_workspace_bytes(e, 1, T) */
 int sopro_mimi_decode_stream(sopro_engine* e, void* workspace, sopro_mimi_stream_state* st, const int32_t* tokens, int32_t T, float* wav,
                              void* stream);
+
+/* ---- batched streaming decode: `rows` utterances (1..64) streamed in LOCKSTEP - they start together and share the frames per
+ * call, the cache policy, and therefore the cache length and the RoPE position at every call; each has its own cached keys /
+ * values.  A separate struct: sopro_mimi_stream_state is unchanged.  `kv` is a caller-owned device buffer of
+ * sopro_mimi_stream_batch_kv_bytes(e, rows, cap_rows) bytes (16-byte aligned), laid out
+ * [layers][2 halves][rows_cap][cap_rows][2 * hidden]; live utterances are slots 0..rows-1 (compacted).
+ * sopro_mimi_stream_batch_init: refuses rows < 1, rows > 64, cap_rows < window.
+ * sopro_mimi_stream_batch_trim: the legacy policy, as sopro_mimi_stream_trim (for all rows at once).
+ * sopro_mimi_stream_batch_keep: drop finished utterances.  `keep` is a HOST array of n_keep strictly increasing indices below
+ *   `rows`; the kept utterances' kv_len cache rows are gathered into the other half (free at every call boundary under both
+ *   policies) in one launch, `half` flips and `rows` becomes n_keep.  Slot i of the next call is keep[i] of this one.
+ * sopro_mimi_decode_stream_batch: tokens [rows, T, Q] -> wav [rows, T * 1920]; workspace of sopro_mimi_workspace_bytes(e, rows, T)
+ *   bytes (rows x T must fit one decode chunk: rows <= sopro_mimi_chunk_rows(rows, T)).  kv_len / pos / half are updated as
+ *   sopro_mimi_decode_stream updates them.  Per layer ONE launch appends every utterance's (k | v) rows and, under the evicting
+ *   policy, writes the window - 1 rows the next call keeps into the other half.  The 2-frame overlap and the cropping stay with
+ *   the host, per utterance (sopro_amd/codec.py MimiStreamDecoder.decode_step_batch); a ragged final call pads the shorter
+ *   utterances' tokens (the decoder is causal: padding reaches no earlier sample) and drops them with _keep afterwards. */
+#define SOPRO_MIMI_STREAM_BATCH_MAX_ROWS 64
+typedef struct sopro_mimi_stream_batch {
+  float* kv;                    /* [layers][2 halves][rows_cap][cap_rows][2 * hidden] post-RoPE (k | v) rows */
+  int32_t rows_cap, rows;       /* buffer sized for rows_cap utterances; live ones are 0..rows-1 (compacted) */
+  int32_t cap_rows, kv_len, pos, evict, half;  /* shared by all live utterances (lockstep) */
+} sopro_mimi_stream_batch;
+int64_t sopro_mimi_stream_batch_kv_bytes(const sopro_engine* e, int32_t rows, int32_t cap_rows);
+int sopro_mimi_stream_batch_init(const sopro_engine* e, sopro_mimi_stream_batch* st, void* kv, int32_t rows, int32_t cap_rows);
+int sopro_mimi_stream_batch_trim(sopro_mimi_stream_batch* st, int32_t n);
+int sopro_mimi_stream_batch_keep(const sopro_engine* e, sopro_mimi_stream_batch* st, const int32_t* keep, int32_t n_keep, void* stream);
+int sopro_mimi_decode_stream_batch(sopro_engine* e, void* workspace, sopro_mimi_stream_batch* st, const int32_t* tokens, int32_t T, float* wav,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

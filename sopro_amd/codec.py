@@ -54,6 +54,34 @@ class MimiDecodeState:
         return bool(self.cst.evict) if self.cst is not None else True
 
 
+@dataclass
+class MimiStreamBatchState:
+    """The streaming state of several utterances decoded in lockstep (``MimiStreamDecoder.decode_step_batch``): the C side's
+    ``sopro_mimi_stream_batch`` (one cache length / position for all, a cache block per utterance) plus, per live utterance, the
+    codes of its last overlap frames (``tails`` [rows, k, Q] int32 on the device)."""
+
+    cst: Optional["hip.MimiStreamBatch"] = None
+    kv_buf: Optional[torch.Tensor] = None
+    tails: Optional[torch.Tensor] = None
+    padded: Tuple[int, ...] = ()  # live rows whose last chunk was padded to the longest: they must leave with the next call
+
+    @property
+    def rows(self) -> int:
+        return int(self.cst.rows) if self.cst is not None else 0
+
+    @property
+    def kv_len(self) -> int:
+        return int(self.cst.kv_len) if self.cst is not None else 0
+
+    @property
+    def pos(self) -> int:
+        return int(self.cst.pos) if self.cst is not None else 0
+
+    @property
+    def evict(self) -> bool:
+        return bool(self.cst.evict) if self.cst is not None else True
+
+
 class MimiCodec:
     def __init__(self, weights: Dict[str, "np.ndarray"], mc: Optional[MimiDecoderConfig] = None, device: str = "cuda:0",
                  precision: str = "f32"):
@@ -258,6 +286,42 @@ class MimiCodec:
         return wav
 
 
+    @torch.inference_mode()
+    def decode_stream_batch(self, codes_btq: torch.Tensor, state: MimiStreamBatchState, cap_rows: Optional[int] = None) -> torch.Tensor:
+        """[B, T, Q] codes of B utterances streamed in lockstep -> [B, T*1920]: ``sopro_mimi_decode_stream_batch``, every utterance
+        attending over its own cached keys / values of earlier calls.  The first call allocates the cache for B utterances of
+        ``cap_rows`` rows each (default: ``stream_cap_rows``); later calls must pass ``state.rows`` utterances."""
+        import ctypes as C
+
+        B, T, Q = codes_btq.shape
+        if Q != self.num_quantizers:
+            raise ValueError(f"expected {self.num_quantizers} codebooks, got {Q}")
+        if self.eng is None:
+            raise hip.SoproHipError("this Mimi checkpoint was loaded without its decoder-side tensors")
+        if T == 0:
+            return torch.zeros(B, 0, device=self.device)
+        lib, eng, dev, ws = hip.load(), self.eng, self.device, self.ws
+        if state.cst is not None and B != state.rows:
+            raise ValueError(f"the batched stream state holds {state.rows} utterances, got {B}")
+        hop = int(self.mc.frame_samples)
+        with self.on_stream():
+            if state.cst is None:
+                cap = int(cap_rows if cap_rows is not None else self.stream_cap_rows)
+                state.kv_buf = torch.empty(int(lib.sopro_mimi_stream_batch_kv_bytes(eng.h, B, cap)), dtype=torch.uint8, device=dev)
+                state.cst = hip.MimiStreamBatch()
+                hip._check(lib.sopro_mimi_stream_batch_init(eng.h, C.byref(state.cst), state.kv_buf.data_ptr(), B, cap), "sopro_mimi_stream_batch_init")
+            src = codes_btq
+            if not (src.is_cuda and src.device == dev and src.dtype == torch.int32 and src.is_contiguous()):
+                src = ws.get(f"rvq.stok.{B}x{T}", (B, T, Q), dtype=torch.int32)
+                src.copy_(codes_btq.to(dev))
+            scratch = ws.get(f"mimi.stage_ws.{B}x{T}", (int(lib.sopro_mimi_workspace_bytes(eng.h, B, T)),), dtype=torch.uint8)
+            wav = torch.empty(B, T * hop, device=dev)
+            hip._check(lib.sopro_mimi_decode_stream_batch(eng.h, scratch.data_ptr(), C.byref(state.cst), src.data_ptr(), T, wav.data_ptr(), hip._stream()),
+                       "sopro_mimi_decode_stream_batch")
+        self.stream.synchronize()
+        return wav
+
+
 class MimiStreamDecoder:
     """Chunked decode with a 2-frame token overlap and a growing transformer cache
     (reference: src/sopro/codec/mimi.py:83-181).  The reference's output depends on the installed transformers (quirk Q6):
@@ -303,3 +367,62 @@ class MimiStreamDecoder:
         keep = min(self.overlap_frames, int(codes_in.shape[0]))
         st.tail_codes_tq = codes_in[-keep:].clone() if self.overlap_frames > 0 else None
         return wav, st
+
+    @torch.inference_mode()
+    def decode_step_batch(self, chunks: Sequence[Optional[torch.Tensor]], state: Optional[MimiStreamBatchState] = None
+                          ) -> Tuple[List[Optional[torch.Tensor]], MimiStreamBatchState]:
+        """``decode_step`` for several utterances in lockstep, one call into the library.  ``chunks``: one entry per live utterance
+        of ``state`` (in its order) - a [n_b, Q] code tensor, or None for an utterance that has finished: it leaves the batch
+        (``sopro_mimi_stream_batch_keep``) and the next call's list no longer has its entry.  The overlap and the cropping are per
+        utterance; a ragged chunk set (a final chunk shorter than the others) is padded to the longest - the decoder is causal, so the
+        padding reaches no sample that is returned - and a padded utterance must leave with the next call.
+        -> (one [1, n_b * 1920] waveform or None per entry of ``chunks``, state)."""
+        import ctypes as C
+
+        st = state or MimiStreamBatchState()
+        codec, dev = self.codec, self.codec.device
+        hop, Q = int(codec.mc.frame_samples), codec.num_quantizers
+        live = [i for i, c in enumerate(chunks) if c is not None]
+        if st.cst is not None and len(chunks) != st.rows:
+            raise ValueError(f"one chunk (or None) per live utterance: {st.rows} expected, got {len(chunks)}")
+        for r in st.padded:
+            if chunks[r] is not None:
+                raise ValueError("an utterance whose last chunk was padded must leave the batch")
+        for i in live:
+            if chunks[i].dim() != 2 or int(chunks[i].shape[0]) == 0 or int(chunks[i].shape[1]) != Q:
+                raise ValueError("every chunk is [n >= 1, Q] (None for a finished utterance)")
+        out: List[Optional[torch.Tensor]] = [None] * len(chunks)
+        if not live:
+            return out, st
+        tails = st.tails
+        if st.cst is not None and len(live) < st.rows:
+            keep = (C.c_int32 * len(live))(*live)
+            with codec.on_stream():
+                hip._check(hip.load().sopro_mimi_stream_batch_keep(codec.eng.h, C.byref(st.cst), keep, len(live), hip._stream()),
+                           "sopro_mimi_stream_batch_keep")
+            if tails is not None:
+                tails = tails[torch.tensor(live, device=dev)]
+        ns = [int(chunks[i].shape[0]) for i in live]
+        nmax = max(ns)
+        ov = min(self.overlap_frames, int(tails.shape[1])) if (self.overlap_frames > 0 and tails is not None) else 0
+        with codec.on_stream():
+            rows = [chunks[i].to(dev) for i in live]
+            if min(ns) < nmax:  # pad the short final chunks by repeating their last frame
+                rows = [c if c.shape[0] == nmax else torch.cat([c, c[-1:].expand(nmax - c.shape[0], Q)], dim=0) for c in rows]
+            new = torch.stack(rows).to(torch.int32)
+            codes_in = torch.cat([tails[:, -ov:], new], dim=1).contiguous() if ov > 0 else new.contiguous()
+        if self.trim == "legacy" and ov > 0 and st.cst is not None and st.kv_len > 0:
+            hip._check(hip.load().sopro_mimi_stream_batch_trim(C.byref(st.cst), ov), "sopro_mimi_stream_batch_trim")
+        if st.cst is None:
+            # the evicting policy keeps window - 1 rows + a call's own (2 per frame; calls never grow past the first); the legacy
+            # policy's plain layers keep everything (as decode_step)
+            cap = 4096 if self.trim == "legacy" else int(codec.mc.sliding_window) - 1 + 2 * (nmax + self.overlap_frames)
+        else:
+            cap = None
+        wav = codec.decode_stream_batch(codes_in, st, cap_rows=cap)
+        for r, i in enumerate(live):
+            out[i] = wav[r:r + 1, ov * hop:(ov + ns[r]) * hop]
+        keep_n = min(self.overlap_frames, int(codes_in.shape[1]))
+        st.tails = codes_in[:, -keep_n:].clone() if self.overlap_frames > 0 else None
+        st.padded = tuple(r for r, n in enumerate(ns) if n < nmax)
+        return out, st

@@ -758,3 +758,71 @@ int sopro_cvt_bf16_f32(const void* src, float* dst, int64_t n, void* stream) {
 }
 
 }  // extern "C"
+
+// ---- the batched streaming decoder's cache (sopro_mimi_stream_batch, csrc/stages.hip): rows of 2 * hidden floats, 16-byte accesses
+namespace {
+
+// One workgroup per (destination row, utterance) of ONE layer.  Blocks j < n append this call's (k | v) rows, read from the qkv
+// buffer (row b * n + j, columns [HS, 3 HS)), at kv_len + j of the utterance's cache in the current half.  Blocks j >= n (the
+// evicting policy, kv_len + n > window - 1) write what the next call keeps, the last nkeep = window - 1 positions, into the OTHER
+// half: older positions from the cache (p < kv_len: rows no block of this launch writes), newer ones straight from qkv - so the
+// launch has no read-after-write inside itself and the attention that follows (current half only) races with nothing.
+__global__ __launch_bounds__(256) void stream_batch_append_kernel(float4* __restrict__ cur, float4* __restrict__ other, const float4* __restrict__ qkv,
+                                                                  int hs4, int64_t bstride4, int n, int kv_len, int keep_from) {
+  const int j = blockIdx.x, b = blockIdx.y;
+  const int row4 = 2 * hs4;
+  const float4* src;
+  float4* dst;
+  if (j < n) {
+    src = qkv + ((int64_t)b * n + j) * 3 * hs4 + hs4;
+    dst = cur + (int64_t)b * bstride4 + (int64_t)(kv_len + j) * row4;
+  } else {
+    const int i = j - n, p = keep_from + i;
+    src = p < kv_len ? cur + (int64_t)b * bstride4 + (int64_t)p * row4 : qkv + ((int64_t)b * n + (p - kv_len)) * 3 * hs4 + hs4;
+    dst = other + (int64_t)b * bstride4 + (int64_t)i * row4;
+  }
+  for (int c = threadIdx.x; c < row4; c += blockDim.x) dst[c] = src[c];
+}
+
+struct KeepMap {
+  int32_t src[64];
+};
+
+// Compaction of the live utterances (sopro_mimi_stream_batch_keep): kept utterance i's kv_len rows of every layer, current half ->
+// slot i of the other half.  One workgroup per (position, kept utterance, layer).
+__global__ __launch_bounds__(256) void stream_batch_gather_kernel(float4* __restrict__ kv, const KeepMap km, int row4, int64_t bstride4, int64_t half4,
+                                                                  int half) {
+  const int p = blockIdx.x, i = blockIdx.y, l = blockIdx.z;
+  const float4* src = kv + (int64_t)(2 * l + half) * half4 + (int64_t)km.src[i] * bstride4 + (int64_t)p * row4;
+  float4* dst = kv + (int64_t)(2 * l + (half ^ 1)) * half4 + (int64_t)i * bstride4 + (int64_t)p * row4;
+  for (int c = threadIdx.x; c < row4; c += blockDim.x) dst[c] = src[c];
+}
+
+}  // namespace
+
+// (internal: called by csrc/stages.hip)  cur / other: the layer's two halves; bstride: floats between utterances (cap_rows * 2 hs)
+int sopro_stream_batch_append(float* cur, float* other, const float* qkv, int32_t hs, int32_t rows, int64_t bstride, int32_t n, int32_t kv_len,
+                              int32_t nkeep, hipStream_t s) {
+  SOPRO_CHECK_ARG(cur && other && qkv && hs > 0 && (hs & 3) == 0 && rows > 0 && n > 0 && kv_len >= 0 && nkeep >= 0 && nkeep <= kv_len + n &&
+                      (int64_t)(kv_len + n) * 2 * hs <= bstride && (int64_t)nkeep * 2 * hs <= bstride && (bstride & 3) == 0,
+                  "bad sizes");
+  SOPRO_CHECK_ARG(aligned16(cur) && aligned16(other) && aligned16(qkv), "16-byte aligned rows");
+  hipLaunchKernelGGL(stream_batch_append_kernel, dim3(n + nkeep, rows), dim3(256), 0, s, reinterpret_cast<float4*>(cur),
+                     reinterpret_cast<float4*>(other), reinterpret_cast<const float4*>(qkv), hs / 4, bstride / 4, n, kv_len, kv_len + n - nkeep);
+  SOPRO_LAUNCH_CHECK();
+}
+
+// kv: [layers][2 halves][rows_cap][bstride floats]
+int sopro_stream_batch_gather(float* kv, const int32_t* keep, int32_t n_keep, int32_t layers, int32_t rows_cap, int64_t bstride, int32_t hs, int32_t half,
+                              int32_t kv_len, hipStream_t s) {
+  SOPRO_CHECK_ARG(kv && keep && n_keep > 0 && n_keep <= 64 && n_keep <= rows_cap && layers > 0 && hs > 0 && (hs & 3) == 0 && kv_len > 0 &&
+                      (int64_t)kv_len * 2 * hs <= bstride && (bstride & 3) == 0 && (half == 0 || half == 1),
+                  "bad sizes");
+  SOPRO_CHECK_ARG(aligned16(kv), "16-byte aligned cache");
+  KeepMap km;
+  for (int i = 0; i < 64; ++i) km.src[i] = i < n_keep ? keep[i] : 0;
+  for (int i = 0; i < n_keep; ++i) SOPRO_CHECK_ARG(keep[i] >= 0 && keep[i] < rows_cap, "kept row outside the buffer");
+  hipLaunchKernelGGL(stream_batch_gather_kernel, dim3(kv_len, n_keep, layers), dim3(256), 0, s, reinterpret_cast<float4*>(kv), km, hs / 2,
+                     bstride / 4, (int64_t)rows_cap * bstride / 4, half);
+  SOPRO_LAUNCH_CHECK();
+}

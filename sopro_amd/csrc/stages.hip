@@ -12,6 +12,12 @@
 
 #include "common.h"
 
+// (elementwise.hip) the batched streaming decoder's cache: append + evict of one layer, compaction of the live utterances
+int sopro_stream_batch_append(float* cur, float* other, const float* qkv, int32_t hs, int32_t rows, int64_t bstride, int32_t n, int32_t kv_len,
+                              int32_t nkeep, hipStream_t s);
+int sopro_stream_batch_gather(float* kv, const int32_t* keep, int32_t n_keep, int32_t layers, int32_t rows_cap, int64_t bstride, int32_t hs, int32_t half,
+                              int32_t kv_len, hipStream_t s);
+
 namespace {
 
 struct Ten {
@@ -1180,7 +1186,7 @@ int64_t sopro_mimi_workspace_bytes(const sopro_engine* e, int32_t B, int32_t T) 
 // encoder's ("etr", fp32 operands).  y [B n, HS], qkv [B n, 3 HS], ao [B n, HS], hd [B n, inter] are scratch.
 static int transformer_stack(sopro_engine* e, hipStream_t s, const char* pre, float* X, int PADX, int64_t xs, float* y, float* qkv, float* ao,
                              float* hd, const SplitK* sk, int B, int n, int past, sopro_mimi_stream_state* sst, int attn_split = 0,
-                             float* lnst = nullptr) {
+                             float* lnst = nullptr, sopro_mimi_stream_batch* sbt = nullptr) {
   const sopro_engine_cfg& c = e->c;
   const int HS = c.mimi_hidden, H = c.mimi_heads, dh = c.mimi_head_dim;
   struct { float *X, *y, *qkv, *ao, *hd; SplitK sk; } w{X, y, qkv, ao, hd, sk ? *sk : SplitK()};
@@ -1217,7 +1223,20 @@ static int transformer_stack(sopro_engine* e, hipStream_t s, const char* pre, fl
     a.Q = w.qkv; a.ldq = 3 * HS; a.q_bstride = (int64_t)n * 3 * HS;
     a.O = w.ao; a.ldo = HS; a.o_bstride = (int64_t)n * HS;
     a.B = B; a.H = H; a.dh = dh; a.Tq = n; a.causal = 1; a.window = c.mimi_window; a.scale = 1.0f / sqrtf((float)dh);
-    if (!sst) {
+    if (sbt) {
+      // the batched streaming cache (all utterances in lockstep: one kv_len, one position): ONE launch appends every utterance's
+      // (k | v) rows and, under the evicting policy, writes the rows the next call keeps into the other half; the attention then
+      // reads utterance b's keys / values cap_rows rows apart in the current half
+      const int64_t bst = (int64_t)sbt->cap_rows * 2 * HS;
+      float* cache = sbt->kv + (size_t)(l * 2 + sbt->half) * sbt->rows_cap * bst;
+      float* other = sbt->kv + (size_t)(l * 2 + (sbt->half ^ 1)) * sbt->rows_cap * bst;
+      const int Tk = sbt->kv_len + n;
+      const int nkeep = (sbt->evict && Tk > c.mimi_window - 1) ? c.mimi_window - 1 : 0;
+      STG(sopro_stream_batch_append(cache, other, w.qkv, HS, B, bst, n, sbt->kv_len, nkeep, s));
+      a.K = cache; a.ldk = 2 * HS; a.k_bstride = bst;
+      a.V = cache + HS; a.ldv = 2 * HS; a.v_bstride = bst;
+      a.Tk = Tk; a.q_pos0 = past; a.k_pos0 = past + n - Tk;
+    } else if (!sst) {
       a.K = w.qkv + HS; a.ldk = 3 * HS; a.k_bstride = (int64_t)n * 3 * HS;
       a.V = w.qkv + 2 * HS; a.ldv = 3 * HS; a.v_bstride = (int64_t)n * 3 * HS;
       a.Tk = n;
@@ -1267,16 +1286,17 @@ static int transformer_stack(sopro_engine* e, hipStream_t s, const char* pre, fl
     if (parts & 1) STG(call);      \
   } while (0)
 static int mimi_decode_core(sopro_engine* e, void* workspace, const int32_t* tokens, int32_t B, int32_t T, float* wav, void* stream,
-                            sopro_mimi_stream_state* sst, int parts = 3) {
+                            sopro_mimi_stream_state* sst, int parts = 3, sopro_mimi_stream_batch* sbt = nullptr) {
   SOPRO_CHECK_ARG(e && e->final && e->has_mimi && workspace && tokens && wav && B > 0 && T > 0,
                   "bad arguments (finalize the engine with the Mimi tensors first)");
   hipStream_t s = (hipStream_t)stream;
   const sopro_engine_cfg& c = e->c;
   const int Q = c.num_codebooks, HS = c.mimi_hidden, CD = c.mimi_codebook_dim, N2 = 2 * T, PADX = c.mimi_kernel - 1;
   const int ns = c.mimi_n_semantic;
-  const int past = sst ? sst->pos : 0;
+  const int past = sst ? sst->pos : sbt ? sbt->pos : 0;
   SOPRO_CHECK_ARG(past + N2 <= c.mimi_rope_positions, "more positions than the RoPE tables hold");
   SOPRO_CHECK_ARG(!sst || (B == 1 && sst->kv && sst->kv_len + N2 <= sst->cap_rows), "streaming state: one utterance, kv_len + 2T <= cap_rows");
+  SOPRO_CHECK_ARG(!sbt || (!sst && B == sbt->rows && sbt->kv && sbt->kv_len + N2 <= sbt->cap_rows), "batched streaming state: B == rows, kv_len + 2T <= cap_rows");
   SOPRO_CHECK_ARG(c.mimi_res_kernel == 3 && c.mimi_last_kernel == 3 && c.mimi_compress == 2, "the SEANet sequence is written for k = 3 residual / last convs, compress 2");
   MimiWs w;
   mimi_carve(e, w, workspace, B, T);
@@ -1311,7 +1331,7 @@ static int mimi_decode_core(sopro_engine* e, void* workspace, const int32_t* tok
   static const bool attn_exact = SOPRO_DEV_ENV("SOPRO_ATTN_SPLIT") != nullptr && SOPRO_DEV_ENV("SOPRO_ATTN_SPLIT")[0] == '0';
   static const bool attn_one = SOPRO_DEV_ENV("SOPRO_ATTN_PASSES") != nullptr && SOPRO_DEV_ENV("SOPRO_ATTN_PASSES")[0] == '1';
   const int attn_split = attn_exact ? 0 : ((c.precision == 1 && attn_one) ? 1 : 3);
-  BODY(transformer_stack(e, s, "tr", w.X, PADX, xs, w.y, w.qkv, w.ao, w.hd, &w.sk, B, N2, past, sst, attn_split, w.lnst));
+  BODY(transformer_stack(e, s, "tr", w.X, PADX, xs, w.y, w.qkv, w.ao, w.hd, &w.sk, B, N2, past, sst, attn_split, w.lnst, sbt));
   static const bool three = SOPRO_DEV_ENV("SOPRO_SEANET_PASSES3") != nullptr;  // developer A/B: the fused kernels' three-pass form in bf16 mode too
   const int sea_passes = (c.precision == 1 && !three) ? 1 : 3;
   // ---- SEANet decoder (HF:931-961), activated-copy flow of sopro_amd.codec.MimiCodec._seanet_act
@@ -1621,6 +1641,71 @@ int sopro_mimi_decode_stream(sopro_engine* e, void* workspace, sopro_mimi_stream
   SOPRO_CHECK_ARG(st != nullptr, "state is NULL");
   const int n = 2 * T, Tk = st->kv_len + n;
   const int rc = mimi_decode_core(e, workspace, tokens, 1, T, wav, stream, st);
+  if (rc != 0) return rc;
+  if (st->evict && Tk > e->c.mimi_window - 1) {
+    st->kv_len = e->c.mimi_window - 1;
+    st->half ^= 1;
+  } else {
+    st->kv_len = Tk;
+  }
+  st->pos += n;
+  return 0;
+}
+
+// ---- batched streaming decode: `rows` utterances in lockstep (one kv_len / pos / policy), each with its own cache rows
+int64_t sopro_mimi_stream_batch_kv_bytes(const sopro_engine* e, int32_t rows, int32_t cap_rows) {
+  if (!e || rows <= 0 || cap_rows <= 0) return 0;
+  return (int64_t)e->c.mimi_layers * 2 * rows * cap_rows * 2 * e->c.mimi_hidden * 4;
+}
+
+int sopro_mimi_stream_batch_init(const sopro_engine* e, sopro_mimi_stream_batch* st, void* kv, int32_t rows, int32_t cap_rows) {
+  SOPRO_CHECK_ARG(e && st && kv, "NULL argument");
+  SOPRO_CHECK_ARG(rows >= 1 && rows <= SOPRO_MIMI_STREAM_BATCH_MAX_ROWS, "rows must be in [1, 64]");
+  SOPRO_CHECK_ARG(cap_rows >= e->c.mimi_window, "cap_rows below the attention window");
+  SOPRO_CHECK_ARG(aligned16(kv) && (e->c.mimi_hidden & 3) == 0, "the cache buffer must be 16-byte aligned (hidden % 4 == 0)");
+  st->kv = reinterpret_cast<float*>(kv);
+  st->rows_cap = rows; st->rows = rows;
+  st->cap_rows = cap_rows;
+  st->kv_len = 0; st->pos = 0; st->evict = 1; st->half = 0;
+  return 0;
+}
+
+int sopro_mimi_stream_batch_trim(sopro_mimi_stream_batch* st, int32_t n) {
+  SOPRO_CHECK_ARG(st && n >= 0, "bad arguments");
+  if (st->kv_len == 0 || n == 0) return 0;
+  st->kv_len = st->kv_len > n ? st->kv_len - n : 0;
+  st->pos = st->kv_len;
+  st->evict = 0;
+  return 0;
+}
+
+int sopro_mimi_stream_batch_keep(const sopro_engine* e, sopro_mimi_stream_batch* st, const int32_t* keep, int32_t n_keep, void* stream) {
+  SOPRO_CHECK_ARG(e && st && keep, "NULL argument");
+  SOPRO_CHECK_ARG(n_keep >= 1 && n_keep <= st->rows, "n_keep must be in [1, rows]");
+  for (int i = 0; i < n_keep; ++i) {
+    SOPRO_CHECK_ARG(keep[i] >= 0 && keep[i] < st->rows, "kept row index out of range");
+    SOPRO_CHECK_ARG(i == 0 || keep[i] > keep[i - 1], "kept row indices must be strictly increasing");
+  }
+  bool same = n_keep == st->rows;  // (strictly increasing + all rows: the identity)
+  if (same) return 0;
+  if (st->kv_len > 0) {
+    // the other half is free at every call boundary (both policies): gather into it and flip - no in-place overlap
+    STG(sopro_stream_batch_gather(st->kv, keep, n_keep, e->c.mimi_layers, st->rows_cap, (int64_t)st->cap_rows * 2 * e->c.mimi_hidden, e->c.mimi_hidden,
+                                  st->half, st->kv_len, (hipStream_t)stream));
+    st->half ^= 1;
+  }
+  st->rows = n_keep;
+  return 0;
+}
+
+int sopro_mimi_decode_stream_batch(sopro_engine* e, void* workspace, sopro_mimi_stream_batch* st, const int32_t* tokens, int32_t T, float* wav,
+                                   void* stream) {
+  SOPRO_CHECK_ARG(st != nullptr, "state is NULL");
+  SOPRO_CHECK_ARG(e && st->rows >= 1 && st->rows <= st->rows_cap && T > 0, "bad arguments");
+  // the workspace of sopro_mimi_workspace_bytes(e, rows, T) holds one chunk of rows: the call decodes all rows at once
+  SOPRO_CHECK_ARG(st->rows <= sopro_mimi_chunk_rows(st->rows, T), "rows x T exceeds one decode chunk (sopro_mimi_chunk_rows)");
+  const int n = 2 * T, Tk = st->kv_len + n;
+  const int rc = mimi_decode_core(e, workspace, tokens, st->rows, T, wav, stream, nullptr, 3, st);
   if (rc != 0) return rc;
   if (st->evict && Tk > e->c.mimi_window - 1) {
     st->kv_len = e->c.mimi_window - 1;

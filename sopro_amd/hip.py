@@ -18,7 +18,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsopro_hip.so")
-ABI_VERSION = 41
+ABI_VERSION = 42
 # Host-side A/B switches whose decision is on record (profiles/rNN_experiments.md) are read from the environment only in DEVELOPER
 # mode (SOPRO_DEV=1) - round 6 housekeeping, the Python twin of the library's `make DEV=1`: a product process ignores them.
 DEV_MODE = os.environ.get("SOPRO_DEV", "0") == "1"
@@ -129,6 +129,12 @@ class MimiStreamState(C.Structure):
     _fields_ = [("kv", _p), ("cap_rows", _i32), ("kv_len", _i32), ("pos", _i32), ("evict", _i32), ("half", _i32)]
 
 
+class MimiStreamBatch(C.Structure):
+    """sopro_mimi_stream_batch"""
+    _fields_ = [("kv", _p), ("rows_cap", _i32), ("rows", _i32), ("cap_rows", _i32), ("kv_len", _i32), ("pos", _i32), ("evict", _i32),
+                ("half", _i32)]
+
+
 # every symbol declared in include/sopro_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "sopro_last_error": (C.c_char_p, []),
@@ -226,6 +232,11 @@ SYMBOLS = {
     "sopro_mimi_stream_init": (C.c_int, [_p, C.POINTER(MimiStreamState), _p, _i32]),
     "sopro_mimi_stream_trim": (C.c_int, [C.POINTER(MimiStreamState), _i32]),
     "sopro_mimi_decode_stream": (C.c_int, [_p, _p, C.POINTER(MimiStreamState), _p, _i32, _p, _p]),
+    "sopro_mimi_stream_batch_kv_bytes": (_i64, [_p, _i32, _i32]),
+    "sopro_mimi_stream_batch_init": (C.c_int, [_p, C.POINTER(MimiStreamBatch), _p, _i32, _i32]),
+    "sopro_mimi_stream_batch_trim": (C.c_int, [C.POINTER(MimiStreamBatch), _i32]),
+    "sopro_mimi_stream_batch_keep": (C.c_int, [_p, C.POINTER(MimiStreamBatch), C.POINTER(_i32), _i32, _p]),
+    "sopro_mimi_decode_stream_batch": (C.c_int, [_p, _p, C.POINTER(MimiStreamBatch), _p, _i32, _p, _p]),
     "sopro_ar_init": (C.c_int, [C.POINTER(ArState), _p]),
     "sopro_ar_sample": (C.c_int, [C.POINTER(ArState), _p, _i64, _p]),
     "sopro_ar_admit": (C.c_int, [C.POINTER(ArState), _i32, _p]),

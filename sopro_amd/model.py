@@ -1043,6 +1043,12 @@ class _ARRun:
         with torch.cuda.stream(self.m.stream):
             return self.plan.hist[0, t0:t1].tolist()
 
+    def tokens_host_batch(self, t0: int, t1: int) -> "np.ndarray":
+        """Every row's codebook-0 tokens of frames [t0, t1) as one [B, t1 - t0] int32 array: ONE device-to-host copy (batched
+        streaming reads a chunk of all rows per step; a row's first EOS is the first entry equal to the EOS id)."""
+        with torch.cuda.stream(self.m.stream):
+            return self.plan.hist[:, t0:t1].cpu().numpy()
+
     def history(self, steps: int, clone: bool = True) -> Tuple[torch.Tensor, List[int]]:
         """Token history [B, steps] and the rows' first-EOS frames (-1: none).  ``clone=False``: a view of the plan's own buffer
         (valid until the next run on this plan starts - a scheduler's refinement reads it in place)."""

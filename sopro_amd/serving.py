@@ -16,7 +16,7 @@ import threading
 import time
 from concurrent.futures import Future
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, Iterator, List, Optional, Tuple
 
 import torch
 
@@ -30,6 +30,46 @@ class _Request:
     key: Tuple
     future: Future
     t_submit: float
+    stream: Optional["_StreamSink"] = None  # submit_stream: where the lane puts this row's chunks
+    seed: Optional[int] = None
+
+
+class _StreamSink:
+    """The blocking iterator ``submit_stream`` returns: an unbounded queue the lane fills (a slow or absent reader never holds up the
+    batch), ended by a sentinel or an exception.  A consumer that closes it or drops it makes its row leave the batch."""
+
+    _END = object()
+
+    def __init__(self):
+        self.q: "queue.Queue[Any]" = queue.Queue()
+        self.cancelled = threading.Event()
+        self._done = False
+
+    def put(self, item) -> None:
+        if not self.cancelled.is_set():
+            self.q.put(item)
+
+    def __iter__(self) -> "Iterator[torch.Tensor]":
+        return self
+
+    def __next__(self) -> torch.Tensor:
+        if self._done:
+            raise StopIteration
+        item = self.q.get()
+        if item is self._END:
+            self._done = True
+            raise StopIteration
+        if isinstance(item, BaseException):
+            self._done = True
+            raise item
+        return item
+
+    def close(self) -> None:
+        self._done = True
+        self.cancelled.set()
+
+    def __del__(self):
+        self.cancelled.set()
 
 
 class SynthesisService:
@@ -42,7 +82,7 @@ class SynthesisService:
 
         self.tts = tts
         self._closed = False
-        self.stats = {"requests": 0, "batches": 0, "rows": 0}
+        self.stats = {"requests": 0, "batches": 0, "rows": 0, "stream_batches": 0}
         self.engine = None
         if mode == "continuous":
             from .continuous import ContinuousSynthesizer
@@ -92,6 +132,31 @@ class SynthesisService:
         fut: Future = Future()
         self._inbox.put(_Request(ids, ref, key, fut, time.perf_counter()))
         return fut
+
+    def submit_stream(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
+                      anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
+                      text_ids: Optional[torch.Tensor] = None, chunk_frames: int = 6, cache_trim: str = "none",
+                      nar_context_frames: Optional[int] = None, seed: Optional[int] = None) -> Iterator[torch.Tensor]:
+        """Queue one streamed utterance -> a blocking iterator over its [1, n * 1920] chunks (``stream``'s chunks).  Streams with equal
+        parameters are grouped into batches of up to ``max_batch`` rows (within ``max_wait_ms``) and each batch runs as one
+        ``stream_batch`` on a lane, sharing the device with whole-utterance batches (AR lock per chunk, bulk lock for refinement and
+        decoding).  Closing or dropping the iterator drops the row from its batch."""
+        if self._closed:
+            raise RuntimeError("service is closed")
+        if self.engine is not None:
+            raise RuntimeError("submit_stream is not available in mode='continuous' (frame-level admission has no streaming path); "
+                               "use mode='batch'")
+        ids = text_ids if text_ids is not None else self.tts.encode_text(text)
+        if int(ids.numel()) == 0:
+            raise ValueError("empty text")
+        if cache_trim not in ("none", "legacy"):
+            raise ValueError("cache_trim must be 'none' or 'legacy'")
+        ss = float(style_strength if style_strength is not None else self.tts.cfg.style_strength)
+        key = ("stream", int(max_frames), float(top_p), float(temperature), bool(anti_loop), ss, min_gen_frames, int(chunk_frames), cache_trim,
+               nar_context_frames)
+        sink = _StreamSink()
+        self._inbox.put(_Request(ids, ref, key, Future(), time.perf_counter(), stream=sink, seed=seed))
+        return sink
 
     def synthesize(self, text: str, ref: PreparedReference, **kw) -> torch.Tensor:
         return self.submit(text, ref, **kw).result()
@@ -156,6 +221,9 @@ class SynthesisService:
                 batch = self._batches.get()
                 if batch is None:
                     return
+                if batch[0].stream is not None:
+                    self._run_stream_batch(lane, batch, locks)
+                    continue
                 mf, top_p, temp, anti, ss, mg = batch[0].key
                 try:
                     out = lane.synthesize_batch([""] * len(batch), [r.ref for r in batch], max_frames=mf, top_p=top_p, temperature=temp,
@@ -170,3 +238,24 @@ class SynthesisService:
                     for r in batch:
                         if not r.future.done():
                             r.future.set_exception(e)
+
+    def _run_stream_batch(self, lane, batch: List[_Request], locks) -> None:
+        _tag, mf, top_p, temp, anti, ss, mg, cf, trim, nar_ctx = batch[0].key
+        sinks = [r.stream for r in batch]
+        try:
+            it = lane.stream_batch([""] * len(batch), [r.ref for r in batch], chunk_frames=cf, max_frames=mf, top_p=top_p, temperature=temp,
+                                   anti_loop=anti, style_strength=ss, min_gen_frames=mg, seeds=[r.seed for r in batch], cache_trim=trim,
+                                   nar_context_frames=nar_ctx, text_ids=[r.text_ids for r in batch], phase_locks=locks,
+                                   alive=lambda b: not sinks[b].cancelled.is_set())
+            self.stats["stream_batches"] += 1
+            self.stats["requests"] += len(batch)
+            self.stats["rows"] += len(batch)
+            for step in it:
+                for sink, c in zip(sinks, step):
+                    if c is not None:
+                        sink.put(c)
+            for sink in sinks:
+                sink.put(_StreamSink._END)
+        except BaseException as e:  # noqa: BLE001
+            for sink in sinks:
+                sink.put(e)

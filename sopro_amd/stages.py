@@ -328,3 +328,55 @@ class StageStreamDecoder:
         st.synchronize()
         self.tail = codes_in[-min(self.ov, T):].clone() if self.ov > 0 else None
         return wav[:, : (ov + n_new) * hop][:, ov * hop:]
+
+
+class StageStreamBatchDecoder:
+    """``MimiStreamDecoder.decode_step_batch`` over ``sopro_mimi_decode_stream_batch``: several utterances streamed in lockstep, each
+    with its own overlap tail and its own block of the cache; finished utterances leave through ``sopro_mimi_stream_batch_keep``."""
+
+    def __init__(self, eng: StageEngine, rows: int, overlap_frames: int = 2, trim: str = "none", cap_rows: int = 4096):
+        self.eng, self.ov, self.trim = eng, int(overlap_frames), trim
+        lib = eng.lib
+        self.kv = torch.empty(int(lib.sopro_mimi_stream_batch_kv_bytes(eng.h, int(rows), cap_rows)), dtype=torch.uint8, device=eng.device)
+        self.st = hip.MimiStreamBatch()
+        hip._check(lib.sopro_mimi_stream_batch_init(eng.h, C.byref(self.st), self.kv.data_ptr(), int(rows), cap_rows), "sopro_mimi_stream_batch_init")
+        self.tails: Optional[torch.Tensor] = None  # [rows, k, Q] int32
+
+    @torch.inference_mode()
+    def decode_step(self, chunks) -> list:
+        """chunks: one [n_b, Q] tensor or None (finished: leaves) per live utterance -> one [1, n_b * 1920] waveform or None each."""
+        eng, lib = self.eng, self.eng.lib
+        hop = int(eng.tts.codec.mc.frame_samples)
+        if len(chunks) != int(self.st.rows):
+            raise ValueError("one chunk (or None) per live utterance")
+        live = [i for i, c in enumerate(chunks) if c is not None]
+        out = [None] * len(chunks)
+        if not live:
+            return out
+        st = eng.stream
+        st.wait_stream(torch.cuda.current_stream(eng.device))
+        if len(live) < int(self.st.rows):
+            keep = (C.c_int32 * len(live))(*live)
+            hip._check(lib.sopro_mimi_stream_batch_keep(eng.h, C.byref(self.st), keep, len(live), st.cuda_stream), "sopro_mimi_stream_batch_keep")
+            if self.tails is not None:
+                self.tails = self.tails[torch.tensor(live, device=eng.device)]
+        ns = [int(chunks[i].shape[0]) for i in live]
+        nmax = max(ns)
+        rows = [chunks[i].to(eng.device).to(torch.int32) for i in live]
+        rows = [c if c.shape[0] == nmax else torch.cat([c, c[-1:].expand(nmax - c.shape[0], c.shape[1])], dim=0) for c in rows]
+        new = torch.stack(rows)
+        ov = min(self.ov, int(self.tails.shape[1])) if (self.ov > 0 and self.tails is not None) else 0
+        codes_in = (torch.cat([self.tails[:, -ov:], new], dim=1) if ov > 0 else new).contiguous()
+        if self.trim == "legacy" and ov > 0:
+            hip._check(lib.sopro_mimi_stream_batch_trim(C.byref(self.st), ov), "sopro_mimi_stream_batch_trim")
+        B, T = int(codes_in.shape[0]), int(codes_in.shape[1])
+        ws = eng._workspace("mimi", int(lib.sopro_mimi_workspace_bytes(eng.h, B, T)))
+        wav = torch.empty(B, T * hop, device=eng.device)
+        st.wait_stream(torch.cuda.current_stream(eng.device))
+        hip._check(lib.sopro_mimi_decode_stream_batch(eng.h, ws.data_ptr(), C.byref(self.st), codes_in.data_ptr(), T, wav.data_ptr(), st.cuda_stream),
+                   "sopro_mimi_decode_stream_batch")
+        st.synchronize()
+        self.tails = codes_in[:, -min(self.ov, T):].clone() if self.ov > 0 else None
+        for r, i in enumerate(live):
+            out[i] = wav[r:r + 1, ov * hop:(ov + ns[r]) * hop]
+        return out

@@ -8,11 +8,14 @@ regardless of ``min_gen_frames``: streaming.py:114-115) and same yielded shapes 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Iterator, List, Optional
+import contextlib
+import time
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
-from .codec import MimiDecodeState, MimiStreamDecoder
+from .codec import MimiDecodeState, MimiStreamBatchState, MimiStreamDecoder
 from .model import PreparedReference
 
 
@@ -88,3 +91,148 @@ def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_t
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
                            chunk_frames=chunk_frames, **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Batched streaming: B utterances in lockstep (same chunk_frames / max_frames / sampling / style / cache policy; own text, voice, seed
+# and end).  Every step advances the batched AR run by one chunk, refines all emitting rows at once over the shared left-context window
+# and decodes them in one call of the batched stream decoder.  Per row, the chunks are exactly what ``stream()`` yields for that row.
+
+def step_plan(t0: int, t1: int, lens: Sequence[Optional[int]], nar_ctx: int) -> Tuple[int, List[Optional[int]]]:
+    """One lockstep step over AR frames [t0, t1) for the live rows (every one has emitted frames [0, t0) so far).  ``lens[b]``: the
+    row's final history length (its first EOS frame, or max_frames + 1) once known, None while it runs past t1.
+    -> (ws, ends): the refinement window starts at ws = max(0, t0 - nar_ctx) for all rows; row b emits frames [t0, ends[b]) with
+    ends[b] = min(t1, lens[b]), or nothing (None) when that is empty - the reference's ``refine_and_emit(end)`` with
+    ``end <= frames_emitted`` (src/sopro/streaming.py:81-104)."""
+    ws = max(0, int(t0) - int(nar_ctx))
+    ends: List[Optional[int]] = []
+    for L in lens:
+        e = int(t1) if L is None else min(int(t1), int(L))
+        ends.append(e if e > t0 else None)
+    return ws, ends
+
+
+def stream_schedule(lens: Sequence[int], chunk_frames: int, nar_ctx: int, n_frames: int) -> List[Dict[str, object]]:
+    """The whole lockstep schedule for rows whose final history lengths ``lens`` (first EOS frame, else ``n_frames`` =
+    max_frames + 1) are given up front: a list of steps {"t0", "t1", "ws", "ends": one entry per row (None: no chunk)}.  Rows leave
+    after the step whose window reaches their length; steps in which no row emits are left out.  (The host loop learns the lengths
+    step by step from the tokens; a length equal to t1 it learns one step later, which changes no chunk.)"""
+    cf = int(chunk_frames)
+    if cf < 1:
+        raise ValueError("chunk_frames must be >= 1")
+    B = len(lens)
+    live = list(range(B))
+    steps: List[Dict[str, object]] = []
+    t0 = 0
+    while live and t0 < n_frames:
+        t1 = min(t0 + cf, int(n_frames))
+        known = [int(lens[b]) if int(lens[b]) <= t1 else None for b in live]
+        ws, ends_live = step_plan(t0, t1, known, nar_ctx)
+        ends: List[Optional[int]] = [None] * B
+        for b, e in zip(live, ends_live):
+            ends[b] = e
+        if any(e is not None for e in ends):
+            steps.append({"t0": t0, "t1": t1, "ws": ws, "ends": ends})
+        live = [b for b, k in zip(live, known) if k is None]
+        t0 = t1
+    return steps
+
+
+@torch.inference_mode()
+def stream_batch(tts, texts: Sequence[str], refs: Sequence, *, chunk_frames: int = 6, max_frames: int = 400, top_p: float = 0.9,
+                 temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
+                 min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
+                 nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
+                 phase_locks: Optional[tuple] = None, timings: Optional[Dict[str, float]] = None,
+                 alive: Optional[Callable[[int], bool]] = None) -> Iterator[List[Optional[torch.Tensor]]]:
+    """B utterances streamed in lockstep.  Yields, per step, a list of B entries: a [1, n * 1920] chunk or None.  Row b's non-None
+    chunks are what ``stream(texts[b], ref=refs[b], seed=seeds[b], ...)`` yields: same chunk sizes, same stop rule (first EOS).
+    ``seeds``: one per row (None: a fresh take for that row).  ``phase_locks`` = (AR lock, bulk lock): held around the AR advance and
+    around refinement + decode of every step (a serving lane shares its device with whole-utterance batches).  ``timings``: seconds
+    of host wall time accumulated under "ar", "refine", "decode".  ``alive(b)`` (a server): False once row b's consumer has gone - the
+    row then leaves the batch at the next step as if it had ended there."""
+    model = tts.model
+    B = len(texts)
+    if B == 0 or len(refs) != B:
+        raise ValueError("need one reference per text")
+    cf = int(chunk_frames)
+    if cf < 1:
+        raise ValueError("chunk_frames must be >= 1")
+    locks = tuple(phase_locks) if phase_locks is not None else ()
+    ar_lock = locks[0] if len(locks) > 0 else contextlib.nullcontext()
+    bulk_lock = locks[1] if len(locks) > 1 else contextlib.nullcontext()
+    ids = list(text_ids) if text_ids is not None else [tts.encode_text(t) for t in texts]
+    ss = float(style_strength if style_strength is not None else tts.cfg.style_strength)
+    nar_ctx = int(nar_context_frames if nar_context_frames is not None else model.rf_nar())
+    if seeds is not None and len(seeds) != B:
+        raise ValueError("one seed per row")
+    # row b draws what a single-row run with nonce next_nonce(seed_b) draws: its own nonce, row index 0
+    nonces = [model.next_nonce(seeds[b] if seeds is not None else None) for b in range(B)]
+    tm = timings if timings is not None else {}
+    for k in ("ar", "refine", "decode"):
+        tm.setdefault(k, 0.0)
+    prep = model.prepare_conditioning_batch(ids, list(refs), max_frames=max_frames, style_strength=ss)
+    run = model.ar_prepare(prep, top_p=top_p, temperature=temperature, anti_loop=anti_loop, min_gen_frames=min_gen_frames,
+                           nonces=nonces, row_ids=[0] * B)
+    Tar = int(max_frames) + 1
+    eos = int(model.V)
+    dec = MimiStreamDecoder(tts.codec, trim=cache_trim)
+    state: Optional[MimiStreamBatchState] = None
+    hist = np.zeros((B, Tar), dtype=np.int64)
+    lens: List[Optional[int]] = [None] * B
+    live = list(range(B))  # rows that have not ended
+    dec_rows: List[int] = []  # rows in the decoder state's order (those that emitted in its last call)
+    cond = prep["cond_ar"]
+    try:
+        t0 = 0
+        t_ar = time.perf_counter()
+        with ar_lock:
+            run.advance(min(cf, Tar))
+        while live and t0 < Tar:
+            t1 = min(t0 + cf, Tar)
+            if alive is not None:
+                for b in live:
+                    if lens[b] is None and not alive(b):
+                        lens[b] = t0  # (emits nothing more: leaves with this step)
+            with ar_lock:
+                hist[:, t0:t1] = run.tokens_host_batch(t0, t1)
+                for b in live:
+                    if lens[b] is None:
+                        hit = np.nonzero(hist[b, t0:t1] == eos)[0]
+                        if hit.size:
+                            lens[b] = t0 + int(hit[0])
+                        elif t1 == Tar:
+                            lens[b] = Tar
+                still = [b for b in live if lens[b] is None]
+                if still and t1 < Tar:  # the next chunk's frames are generated while this one is refined and decoded
+                    run.advance(min(cf, Tar - t1))
+            tm["ar"] += time.perf_counter() - t_ar
+            ws, ends_live = step_plan(t0, t1, [lens[b] for b in live], nar_ctx)
+            ends = {b: e for b, e in zip(live, ends_live) if e is not None}
+            if ends:
+                em = sorted(ends)
+                e_max = max(ends.values())
+                with bulk_lock:
+                    t_r = time.perf_counter()
+                    idx = torch.tensor(em, device=cond.device)
+                    cond_win = cond.index_select(0, idx)[:, ws:e_max, :]
+                    tok_a = torch.from_numpy(hist[em, ws:e_max])
+                    toks = model.nar_refine(cond_win, tok_a, lens=[ends[b] - ws for b in em])
+                    t_d = time.perf_counter()
+                    tm["refine"] += t_d - t_r
+                    pos = {b: j for j, b in enumerate(em)}
+                    rows = dec_rows if state is not None else em
+                    chunks = [toks[pos[b], t0 - ws:ends[b] - ws, :] if b in ends else None for b in rows]
+                    wavs, state = dec.decode_step_batch(chunks, state)
+                    tm["decode"] += time.perf_counter() - t_d
+                out: List[Optional[torch.Tensor]] = [None] * B
+                for b, w in zip(rows, wavs):
+                    if w is not None and w.numel() > 0:
+                        out[b] = w
+                dec_rows = [b for b in rows if b in ends]
+                yield out
+            live = [b for b in live if lens[b] is None]
+            t0 = t1
+            t_ar = time.perf_counter()
+    finally:
+        run.done = True  # also when the consumer abandons the generator: the plan is free again

@@ -225,6 +225,19 @@ class SoproTTS:
 
         return stream(self, text, **kwargs)
 
+    def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
+                     top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
+                     min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
+                     nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
+                     **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
+        """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
+        entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch)."""
+        from .streaming import stream_batch
+
+        return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
+                            anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
+                            cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, **kwargs)
+
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""
         import wave

@@ -814,6 +814,35 @@ int sopro_mimi_stream_batch_keep(const sopro_engine* e, sopro_mimi_stream_batch*
 int sopro_mimi_decode_stream_batch(sopro_engine* e, void* workspace, sopro_mimi_stream_batch* st, const int32_t* tokens, int32_t T, float* wav,
                                    void* stream);
 
+/* ---- long-form join: a padded batch of utterances -> one continuous waveform -------------------------------------------- */
+/* The sentences of a long text are synthesised as the rows of ordinary batches (sopro_mimi_decode leaves them as wav
+ * [n_seg, row_stride], row k valid for lens[k] samples; nothing past a row's length is ever read).  The join trims each row's silent
+ * head and tail, lays the kept parts end to end with gaps[k] samples of silence after row k, and fades the cuts.  No reference
+ * counterpart (the reference stops at one utterance of 400 frames, its README).  The definition, exact in integers and in fp32:
+ *  1. Edges.  L = lens[k] (clamped to [0, max_len]); peak = max |x[i]|, i < L.  L == 0 or peak == 0: start = end = 0.  Otherwise
+ *     thr = fl32(rel * peak); hop j covers [j hop, min((j + 1) hop, L)) and is active iff its max |x| >= thr; first / last = the lowest /
+ *     highest active hop; start = max(0, (first - keep) hop), end = min(L, (last + 1 + keep) hop).  trim == 0: start = 0, end = L for
+ *     every row (nothing is looked at, workspace may be NULL).  Only maxima are taken - exact in any order - so the edges have one
+ *     right answer (an RMS detector's decision would depend on the order of its sum).  Inputs are taken to be finite; a NaN or an
+ *     infinity may move or empty a row's edges but never leads outside wav[k, 0:L].
+ *  2. Layout.  n_k = end_k - start_k; offs[0] = 0, offs[k + 1] = offs[k] + (n_k > 0 ? n_k + max(gaps[k], 0) : 0) in int64: an empty
+ *     row contributes neither samples nor its gap.  total = offs[n_seg].
+ *  3. Samples.  F = min(fade_len, n_k / 2); for i in [0, n_k): g = tab[i] if i < F, tab[n_k - 1 - i] if i >= n_k - F, else 1;
+ *     out[offs[k] + i] = fl32(x[start_k + i] * g).  Every other sample of out[0 : total] is 0.0f (written by the same launch: no
+ *     memset of out is needed).  Nothing at or past min(total, out_cap) is written: a host that sized out too small sees
+ *     total > out_cap in offs afterwards.  `tab`: fade_len gains on the device, made by the host (the library evaluates no
+ *     trigonometry here); the Python host uses tab[m] = fl32(0.5 - 0.5 cos(pi (m + 0.5) / fade_len)) from float64.
+ * sopro_join_edges_f32 needs sopro_join_workspace_bytes(n_seg, max_len, hop) bytes of device scratch (one float per hop and row;
+ * max_len: a host-side upper bound of lens) and writes edges int32 [n_seg][2]; sopro_join_layout_i64 writes offs int64
+ * [n_seg + 1]; sopro_join_mix_f32 writes out.  All three enqueue on `stream`, allocate nothing and synchronise nothing (they may be
+ * captured), so the three run back to back without the host learning `total` in between. */
+int64_t sopro_join_workspace_bytes(int32_t n_seg, int64_t max_len, int32_t hop);
+int sopro_join_edges_f32(const float* wav, int64_t row_stride, const int32_t* lens, int32_t n_seg, int64_t max_len, int32_t hop, float rel,
+                         int32_t keep, int32_t trim, void* workspace, int32_t* edges, void* stream);
+int sopro_join_layout_i64(const int32_t* edges, const int32_t* gaps, int32_t n_seg, int64_t* offs, void* stream);
+int sopro_join_mix_f32(const float* wav, int64_t row_stride, const int32_t* edges, const int64_t* offs, const float* tab, int32_t fade_len,
+                       int32_t n_seg, float* out, int64_t out_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

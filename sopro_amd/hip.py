@@ -262,6 +262,10 @@ SYMBOLS = {
     "sopro_cvt_bf16_f32": (C.c_int, [_p, _p, _i64, _p]),
     "sopro_prof_enable": (C.c_int, [C.c_int]),
     "sopro_prof_collect": (C.c_int, [_p, _i32, _p]),
+    "sopro_join_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "sopro_join_edges_f32": (C.c_int, [_p, _i64, _p, _i32, _i64, _i32, _f32, _i32, _i32, _p, _p, _p]),
+    "sopro_join_layout_i64": (C.c_int, [_p, _p, _i32, _p, _p]),
+    "sopro_join_mix_f32": (C.c_int, [_p, _i64, _p, _p, _p, _i32, _i32, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -941,6 +945,72 @@ def cvt_f32_bf16(src: torch.Tensor, dst: torch.Tensor, n: Optional[int] = None, 
 def cvt_bf16_f32(src: torch.Tensor, dst: torch.Tensor, n: Optional[int] = None) -> None:
     n = int(src.numel() if n is None else n)
     _check(load().sopro_cvt_bf16_f32(ptr(src, torch.bfloat16), ptr(dst), n, _stream()), "sopro_cvt_bf16_f32")
+
+
+_fade_tabs: dict = {}  # (fade_len, device) -> the join's gain table on the device
+
+
+def fade_table(fade_len: int, device) -> Optional[torch.Tensor]:
+    """tab[m] = fl32(0.5 - 0.5 cos(pi (m + 0.5) / fade_len)), evaluated in float64 on the host and rounded once (the raised-cosine
+    gains ``sopro_join_mix_f32`` applies to the first / last ``fade_len`` kept samples of a segment); None for ``fade_len == 0``."""
+    import numpy as np
+
+    fade_len = int(fade_len)
+    if fade_len <= 0:
+        return None
+    key = (fade_len, str(device))
+    t = _fade_tabs.get(key)
+    if t is None:
+        tab = (0.5 - 0.5 * np.cos(np.pi * (np.arange(fade_len, dtype=np.float64) + 0.5) / fade_len)).astype(np.float32)
+        t = _fade_tabs[key] = torch.from_numpy(tab).to(device)
+    return t
+
+
+def join_segments(wav: torch.Tensor, lens, gaps, *, hop: int = 240, rel: float = 0.01, keep: int = 3, fade_len: int = 120,
+                  trim: bool = True, out: Optional[torch.Tensor] = None):
+    """The long-form join (sopro_join_edges_f32 / _layout_i64 / _mix_f32, contract in include/sopro_hip.h): ``wav`` fp32
+    [n_seg, >= max(lens)] on the device (rows ``wav.stride(0)`` apart: a decoder batch as it is), ``lens`` valid samples per row,
+    ``gaps`` samples of silence after each row (host sequences) -> (out[:total] on the device, edges int32 [n_seg, 2] and offs int64
+    [n_seg + 1] on the host).  ``out`` is allocated at the upper bound sum(lens) + sum(gaps) unless given; the three steps are
+    launched back to back on the current stream and the one host copy of (offs | edges) at the end is the only synchronisation."""
+    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    gaps_h = [int(v) for v in (gaps.tolist() if isinstance(gaps, torch.Tensor) else gaps)]
+    n = len(lens_h)
+    ptr(wav)  # a contiguous-row fp32 tensor on the device, or it raises here
+    if wav.dim() != 2 or int(wav.shape[0]) != n or len(gaps_h) != n:
+        raise SoproHipError(f"join_segments wants wav [n_seg, samples] with one length and one gap per row, got {tuple(wav.shape)}, {n}, {len(gaps_h)}")
+    if n and (min(lens_h) < 0 or min(gaps_h) < 0 or max(lens_h) > int(wav.shape[1])):
+        raise SoproHipError("join_segments: lens must lie in [0, wav.shape[1]] and gaps must not be negative")
+    if int(wav.shape[1]) > 1 and wav.stride(1) != 1:
+        raise SoproHipError("join_segments: the samples of a row must be contiguous")
+    dev = wav.device
+    bound = sum(lens_h) + sum(gaps_h)
+    if out is None:
+        out = torch.empty(bound, dtype=torch.float32, device=dev)
+    elif out.dim() != 1 or not out.is_contiguous():
+        raise SoproHipError("join_segments: out must be a contiguous vector")
+    if n == 0:
+        return out[:0], torch.zeros(0, 2, dtype=torch.int32), torch.zeros(1, dtype=torch.int64)
+    lib = load()
+    max_len = max(lens_h)
+    tab = fade_table(fade_len, dev)
+    with torch.cuda.device(dev):
+        args = torch.tensor([lens_h, gaps_h], dtype=torch.int32).to(dev)  # [2, n]: one upload
+        meta = torch.empty(2 * n + 1, dtype=torch.int64, device=dev)    # offs [n + 1] | edges [n][2] as int32 pairs: one download
+        offs_d, edges_d = meta[: n + 1], meta[n + 1:].view(torch.int32)
+        ws = torch.empty(max(1, int(lib.sopro_join_workspace_bytes(n, max_len, int(hop))) // 4), dtype=torch.float32, device=dev) if trim else None
+        s = _stream()
+        _check(lib.sopro_join_edges_f32(ptr(wav), int(wav.stride(0)), args[0].data_ptr(), n, max_len, int(hop), float(rel), int(keep), int(bool(trim)),
+                                        ptr(ws), edges_d.data_ptr(), s), "sopro_join_edges_f32")
+        _check(lib.sopro_join_layout_i64(edges_d.data_ptr(), args[1].data_ptr(), n, offs_d.data_ptr(), s), "sopro_join_layout_i64")
+        _check(lib.sopro_join_mix_f32(ptr(wav), int(wav.stride(0)), edges_d.data_ptr(), offs_d.data_ptr(), ptr(tab), int(fade_len), n, ptr(out),
+                                      int(out.numel()), s), "sopro_join_mix_f32")
+        host = meta.cpu()
+    offs, edges = host[: n + 1].clone(), host[n + 1:].view(torch.int32).reshape(n, 2).clone()
+    total = int(offs[n])
+    if total > int(out.numel()):
+        raise SoproHipError(f"join_segments: the joined waveform has {total} samples, out holds {int(out.numel())}")
+    return out[:total], edges, offs
 
 
 def set_host_wait(blocking: bool, device=None) -> None:

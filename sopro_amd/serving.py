@@ -158,6 +158,53 @@ class SynthesisService:
         self._inbox.put(_Request(ids, ref, key, Future(), time.perf_counter(), stream=sink, seed=seed))
         return sink
 
+    def submit_long(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
+                    anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
+                    max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0,
+                    keep_ms: float = 30.0, fade_ms: float = 5.0, keep_parts: bool = False) -> "Future":
+        """Queue a text of any length -> a future of ``longform.LongformResult`` (``SoproTTS.synthesize_long``'s result).  The text is
+        split here and every segment goes through ``submit``, so the scheduler batches the segments with whatever else is queued;
+        a small waiter thread gathers the segment futures in order, stacks them into one padded tensor and joins them on the
+        device (``hip.join_segments``).  The sampler draws as ``submit`` draws (a fresh take per segment: no seed, no group plan)."""
+        from . import hip
+        from .longform import LongformPart, LongformResult, join_params, pause_samples, split_text
+
+        if self._closed:
+            raise RuntimeError("service is closed")
+        if self.engine is not None:
+            raise RuntimeError("submit_long is not available in mode='continuous'; use mode='batch'")
+        segs = split_text(text, max_chars=max_chars)
+        gaps = [pause_samples(s.boundary, pauses_ms) for s in segs]
+        join_kw = join_params(trim_db, keep_ms, fade_ms)
+        futs = [self.submit(s.text, ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
+                            style_strength=style_strength, min_gen_frames=min_gen_frames) for s in segs]
+        done: Future = Future()
+        dev = self.tts.device
+
+        def gather() -> None:
+            try:
+                if not segs:
+                    done.set_result(LongformResult(torch.zeros(1, 1, 0, device=dev), [], [], [] if keep_parts else None, [] if keep_parts else None))
+                    return
+                gaps[-1] = 0
+                wavs = [f.result().reshape(-1) for f in futs]
+                lens = [int(w.numel()) for w in wavs]
+                with torch.cuda.device(dev):
+                    # the lanes synchronise their streams before a future resolves: the rows are complete when they are read here
+                    rows = torch.zeros(len(wavs), max(1, max(lens)), device=dev)
+                    for k, w in enumerate(wavs):
+                        rows[k, : lens[k]] = w
+                    out, edges, offs = hip.join_segments(rows, lens, gaps, **join_kw)
+                o, e = offs.tolist(), edges.tolist()
+                cues = [(segs[k].text, o[k], o[k] + e[k][1] - e[k][0]) for k in range(len(segs))]
+                parts = [LongformPart(w.reshape(1, 1, -1), None) for w in wavs] if keep_parts else None
+                done.set_result(LongformResult(out.reshape(1, 1, -1), cues, [len(segs)], parts, [tuple(x) for x in e] if keep_parts else None))
+            except BaseException as exc:  # noqa: BLE001
+                done.set_exception(exc)
+
+        threading.Thread(target=gather, name="sopro-long", daemon=True).start()
+        return done
+
     def synthesize(self, text: str, ref: PreparedReference, **kw) -> torch.Tensor:
         return self.submit(text, ref, **kw).result()
 

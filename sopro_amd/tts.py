@@ -3,12 +3,13 @@
 Same constructor / method signatures and error behaviour as the reference class, so existing call
 sites (``README.md:69-120``, ``src/sopro/cli.py``, ``demo/server.py:224,241``) keep working; the body
 of every method runs on the MI355X engine (``sopro_amd.model`` / ``sopro_amd.codec``).  Additions
-that the reference does not have: ``synthesize_batch`` and ``from_weights``.
+that the reference does not have: ``synthesize_batch``, ``stream_batch``, ``from_weights`` and the long-form entry points
+``synthesize_long`` / ``stream_long`` (text of any length: split, batched, joined on the device; ``sopro_amd.longform``).
 """
 from __future__ import annotations
 
 import os
-from typing import Any, Dict, Iterator, List, Optional, Sequence
+from typing import Any, Dict, Iterator, List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -17,6 +18,13 @@ from .codec import MimiCodec
 from .config import DEFAULT_MIMI_ID, TARGET_SR, MimiDecoderConfig, SoproTTSConfig
 from .model import PreparedReference, SoproTTSModel
 from .weights import load_cfg_from_safetensors, load_safetensors
+
+
+class PaddedBatch(NamedTuple):
+    """``synthesize_batch(..., padded=True)``: the decoder's batch where it is."""
+    wav: torch.Tensor      # [B, T * 1920] fp32; row b is valid for lens[b] samples
+    lens: List[int]        # samples
+    tokens: torch.Tensor   # [B, T, Q] int64; row b is valid for lens[b] / 1920 frames
 
 
 class SoproTTS:
@@ -137,9 +145,12 @@ class SoproTTS:
                          style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                          timings: Optional[Dict[str, float]] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                          phase_locks: Optional[tuple] = None, seed: Optional[int] = None, nonces: Optional[Sequence[int]] = None,
-                         row_ids: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+                         row_ids: Optional[Sequence[int]] = None, padded: bool = False) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
-        ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun)."""
+        ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
+        ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
+        ``PaddedBatch`` of ``wav`` [B, T * 1920], ``lens`` (valid samples per row) and ``tokens`` [B, T, Q] (a copy: the engine's
+        own token matrix is overwritten by the next pass); the list above is ``[wav[b, :lens[b]].reshape(1, 1, -1)]``."""
         import contextlib
         import time
 
@@ -195,6 +206,8 @@ class SoproTTS:
             lens = [int(n) for n in state["lens"]]
             B, Tn = int(full.shape[0]), int(full.shape[1])
             if max(lens) == 0:
+                if padded:
+                    return PaddedBatch(torch.zeros(B, 0, device=self.device), [0] * B, torch.zeros(B, 0, self.model.Q, dtype=torch.long, device=self.device))
                 return [torch.zeros(1, 1, 0, device=self.device) for _ in range(B)]
             # The padded batch goes to the decoder as it is: the decoder is causal, so the (valid, meaningless) codes a row holds
             # past its own length never reach the samples that are returned.
@@ -212,7 +225,13 @@ class SoproTTS:
                     timings["nar"] = timings.get("nar", 0.0) + (t1 - t0)
                     timings["mimi"] = timings.get("mimi", 0.0) + (time.perf_counter() - t1)
                 timings["_bulk_t1"] = time.perf_counter()
+            toks = None
+            if padded:  # (the engine's own token matrix: copied before the next pass overwrites it, complete before any stream reads it)
+                toks = codes.long()
+                self.model.bulk_stream.synchronize()
         hop = int(self.codec.mc.frame_samples)
+        if padded:
+            return PaddedBatch(wav, [n * hop for n in lens], toks)
         return [wav[b, : lens[b] * hop].reshape(1, 1, -1) for b in range(B)]
 
     def clone_lane(self) -> "SoproTTS":
@@ -237,6 +256,28 @@ class SoproTTS:
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
                             cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, **kwargs)
+
+    def synthesize_long(self, text: str, **kwargs):
+        """New: a text of any length (a paragraph, an article, a chapter) -> ``LongformResult``: ``wav`` [1, 1, N] on the device and
+        ``segments`` [(text, start sample, end sample)] in it.  The text is cut into sentences (``longform.split_text``,
+        ``max_chars``), the voice is prepared once, groups of up to ``max_rows`` segments (``plan``: "throughput", "latency" or a
+        list of group sizes) run through ``synthesize_batch``, and each group's padded decoder batch is joined on the device
+        (``hip.join_segments``): silence below ``trim_db`` of a segment's peak is trimmed to ``keep_ms`` around the speech
+        (``trim_db=None``: nothing is trimmed), pauses follow the kind of boundary (``pauses_ms``), cuts get ``fade_ms`` raised-cosine
+        fades.  ``max_frames`` and the sampling parameters are per segment, as in ``synthesize``; segment k draws as
+        ``synthesize(segment_k, ref=ref, seed=seed + k)`` does.  ``keep_parts=True`` also returns every segment's untrimmed
+        waveform and tokens (``parts``) and the kept range (``edges``).  Full parameter list: ``longform.synthesize_long``."""
+        from .longform import synthesize_long
+
+        return synthesize_long(self, text, **kwargs)
+
+    def stream_long(self, text: str, **kwargs) -> Iterator[torch.Tensor]:
+        """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
+        yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
+        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit."""
+        from .longform import stream_long
+
+        return stream_long(self, text, **kwargs)
 
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""

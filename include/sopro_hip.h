@@ -843,6 +843,50 @@ int sopro_join_layout_i64(const int32_t* edges, const int32_t* gaps, int32_t n_s
 int sopro_join_mix_f32(const float* wav, int64_t row_stride, const int32_t* edges, const int64_t* offs, const float* tab, int32_t fade_len,
                        int32_t n_seg, float* out, int64_t out_cap, void* stream);
 
+/* ---- speaking rate: WSOLA time-scale modification of the rows of a padded batch ------------------------------------------- */
+/* The model has no rate input (text, voice and style only), so a speaking rate is applied to the decoded waveform: waveform-
+ * similarity overlap-add, which changes the duration and keeps the pitch.  No reference counterpart.  24 kHz mono fp32.  The
+ * similarity search runs on integers, so every decision is an exact comparison and every output sample a fixed chain of three fp32
+ * operations: the operator has one right answer, bit for bit (tests/tsm_ref.py restates it in numpy).
+ *   W = 960 (comparison window), HS = 480 (output hop), R = 240 (search radius); tab[n] = fl32(0.5 - 0.5 cos(pi (n + 0.5) / HS)),
+ *   n < HS, made by the host in float64 (the join's fade table of length HS); step = round(speed * HS * 65536), speed in [0.5, 2]:
+ *   the device sees only `step`, clamped to [HS << 15, HS << 17].
+ *   x[0 .. L) is a row; reads at or past L give 0.0 (nothing past a row's length is read from memory).
+ *   M = (L * HS * 65536) / step output samples (integer division) in K = ceil(M / HS) blocks, the last one cut at M.
+ *   Block 0: y[0 .. HS) = x[0 .. HS), p_0 = 0.
+ *   Block k >= 1: a = (k * step) >> 16 (64 bits), t = p_{k-1} + HS, candidates d in [max(-R, -a), R] =: [lo, R].
+ *     m = max |x| over x[a + lo .. a + R + W) and x[t .. t + W).  m == 0: d_k = 0.  Else inv = fl32(127 / m),
+ *     q(v) = rint(fl32(v * inv)) (half to even), ssd[d] = sum_{n < W} (q(x[t + n]) - q(x[a + d + n]))^2 (exact in int32);
+ *     d_k = the d of least ssd, ties to the smaller |d|, then to the positive d.
+ *     p_k = a + d_k; y[k HS + n] = fl32(A + fl32(tab[n] * fl32(B - A))), A = x[t + n], B = x[p_k + n], n < HS (no contraction).
+ *   At step = HS << 16 every block finds ssd = 0 at d = 0 and y == x; wherever p_k == t the output is a copy of the input.
+ * Chunked form (same numbers): `state` holds, per row, (k, p_{k-1}, samples received, the retained input tail).  A call appends
+ * in[row, 0 .. in_lens[row]) to the row and computes every block that is ready: block 0 once received >= HS and M(received) >= HS, block k >= 1 once
+ * received >= max(t, a + R) + W.  Such a block lies wholly below the final M, whatever follows.  With `flush` the remaining blocks
+ * are computed with zero extension, the last one cut at M of the total length, and the row's state is zeroed (a fresh row).  Any
+ * chunking followed by a flush gives the one-shot result bit for bit.  The retained tail is everything from min(t, a - R) on:
+ * a_k - a_{k-1} lies in [240, 960] and |d| <= R, so t - a lies in [-720, 480]; the tail then spans at most (a + R) - (a - 720) =
+ * 960 samples plus the W - 1 that were not yet enough: < 1920 <= SOPRO_TSM_TAIL.
+ * Output of a call: out[row, 0 .. out_lens[row]) = the samples of the blocks computed by THIS call, in order (one-shot: the whole
+ * y).  Nothing at or past out_cap is written; a row whose ready blocks do not fit gets out_lens[row] = -1 and a zeroed state (a
+ * sizing error of the caller: sopro_tsm_out_len gives the exact one-shot size, sopro_tsm_chunk_out_cap(in_cap) a bound for one
+ * chunked call, flush included).  deltas (nullable) int32 [rows][blocks_cap]: d_k of the call's blocks, in order (block 0: 0).
+ * in_lens int32 [rows] (clamped to [0, in_cap]), steps int64 [rows], out_lens int32 [rows], tab float [HS]: device memory.
+ * state: NULL for a one-shot call (flush must be set), else sopro_tsm_state_bytes(rows) bytes of device memory, zeroed before a
+ * row's first chunk.  Rows need no alignment beyond 4 bytes.  sopro_tsm_rows_f32 enqueues one launch (one workgroup per row) on
+ * `stream`, allocates nothing and synchronises nothing; the helpers are host arithmetic (-1: argument out of range). */
+#define SOPRO_TSM_W 960
+#define SOPRO_TSM_HS 480
+#define SOPRO_TSM_R 240
+#define SOPRO_TSM_TAIL 2048
+int64_t sopro_tsm_out_len(int64_t in_len, int64_t step);
+int64_t sopro_tsm_blocks(int64_t out_len);
+int64_t sopro_tsm_chunk_out_cap(int64_t in_len);
+int64_t sopro_tsm_state_bytes(int32_t rows);
+int sopro_tsm_rows_f32(const float* in, int64_t in_stride, const int32_t* in_lens, int64_t in_cap, const int64_t* steps, int32_t rows, void* state,
+                       int32_t flush, const float* tab, float* out, int64_t out_stride, int64_t out_cap, int32_t* out_lens, int32_t* deltas,
+                       int32_t blocks_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

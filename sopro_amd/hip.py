@@ -12,7 +12,7 @@ import ctypes as C
 import gc
 import os
 import threading
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -266,6 +266,11 @@ SYMBOLS = {
     "sopro_join_edges_f32": (C.c_int, [_p, _i64, _p, _i32, _i64, _i32, _f32, _i32, _i32, _p, _p, _p]),
     "sopro_join_layout_i64": (C.c_int, [_p, _p, _i32, _p, _p]),
     "sopro_join_mix_f32": (C.c_int, [_p, _i64, _p, _p, _p, _i32, _i32, _p, _i64, _p]),
+    "sopro_tsm_out_len": (_i64, [_i64, _i64]),
+    "sopro_tsm_blocks": (_i64, [_i64]),
+    "sopro_tsm_chunk_out_cap": (_i64, [_i64]),
+    "sopro_tsm_state_bytes": (_i64, [_i32]),
+    "sopro_tsm_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _i64, _i64, _p, _p, _i32, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1011,6 +1016,148 @@ def join_segments(wav: torch.Tensor, lens, gaps, *, hop: int = 240, rel: float =
     if total > int(out.numel()):
         raise SoproHipError(f"join_segments: the joined waveform has {total} samples, out holds {int(out.numel())}")
     return out[:total], edges, offs
+
+
+# ---- speaking rate (sopro_tsm_*; definition in include/sopro_hip.h, numpy restatement in tests/tsm_ref.py) ----
+TSM_W, TSM_HS, TSM_R = 960, 480, 240
+SPEED_MIN, SPEED_MAX = 0.5, 2.0
+tsm_calls = 0  # launches of sopro_tsm_rows_f32 by this process: the speed == 1.0 paths never add to it
+
+
+def tsm_step(speed) -> int:
+    """round(speed * HS * 65536): all the device sees of a speaking rate.  ``ValueError`` outside [0.5, 2.0]."""
+    try:
+        v = float(speed)
+    except (TypeError, ValueError):
+        raise ValueError(f"speed must be a number in [{SPEED_MIN}, {SPEED_MAX}], got {speed!r}") from None
+    if not (SPEED_MIN <= v <= SPEED_MAX):  # (NaN fails both comparisons)
+        raise ValueError(f"speed must lie in [{SPEED_MIN}, {SPEED_MAX}], got {speed!r}")
+    return int(round(v * TSM_HS * 65536))
+
+
+def tsm_steps(speed, rows: int) -> List[int]:
+    """One step per row from a float or one float per row."""
+    if isinstance(speed, (list, tuple)) or (hasattr(speed, "__len__") and not isinstance(speed, str)):
+        vals = [tsm_step(v) for v in speed]
+        if len(vals) != int(rows):
+            raise ValueError(f"speed: one value or one per row ({rows}), got {len(vals)}")
+        return vals
+    return [tsm_step(speed)] * int(rows)
+
+
+def tsm_out_len(in_len: int, step: int) -> int:
+    """Samples a row of ``in_len`` samples has after the stretch: (in_len * HS * 65536) // step (sopro_tsm_out_len)."""
+    in_len, step = int(in_len), int(step)
+    if in_len < 0 or not (TSM_HS << 15) <= step <= (TSM_HS << 17):
+        raise ValueError("in_len >= 0 and step in [HS << 15, HS << 17]")
+    return (in_len * TSM_HS * 65536) // step
+
+
+def tsm_blocks(out_len: int) -> int:
+    return max(0, -(-int(out_len) // TSM_HS))
+
+
+def _tsm_launch(wav, in_cap: int, lens_h, steps_h, state, flush: bool, out, want_deltas: bool):
+    """One sopro_tsm_rows_f32 on the current stream -> (out_lens on the device, deltas on the device or None, blocks_cap)."""
+    global tsm_calls
+    rows = len(lens_h)
+    dev = out.device
+    lib = load()
+    with torch.cuda.device(dev):
+        args = torch.tensor([steps_h, lens_h], dtype=torch.int64).to(dev)  # one upload
+        in_lens = args[1].to(torch.int32)
+        out_lens = torch.empty(rows, dtype=torch.int32, device=dev)
+        blocks_cap = int(out.shape[1]) // TSM_HS + 1
+        deltas = torch.zeros(rows, blocks_cap, dtype=torch.int32, device=dev) if want_deltas else None
+        tsm_calls += 1
+        _check(lib.sopro_tsm_rows_f32(ptr(wav) if in_cap > 0 else None, int(wav.stride(0)) if in_cap > 0 else 0, in_lens.data_ptr(), int(in_cap),
+                                      args[0].data_ptr(), rows, state.data_ptr() if state is not None else None, int(bool(flush)),
+                                      ptr(fade_table(TSM_HS, dev)), ptr(out), int(out.stride(0)), int(out.shape[1]), out_lens.data_ptr(),
+                                      deltas.data_ptr() if deltas is not None else None, blocks_cap, _stream()), "sopro_tsm_rows_f32")
+    return out_lens, deltas, blocks_cap
+
+
+def _tsm_check_rows(wav: torch.Tensor, lens_h: List[int], what: str) -> None:
+    ptr(wav)
+    if wav.dim() != 2 or int(wav.shape[0]) != len(lens_h):
+        raise SoproHipError(f"{what} wants wav [rows, samples] with one length per row, got {tuple(wav.shape)} and {len(lens_h)} lengths")
+    if lens_h and (min(lens_h) < 0 or max(lens_h) > int(wav.shape[1])):
+        raise SoproHipError(f"{what}: lens must lie in [0, wav.shape[1]]")
+    if int(wav.shape[1]) > 1 and wav.stride(1) != 1:
+        raise SoproHipError(f"{what}: the samples of a row must be contiguous")
+
+
+def time_stretch(wav: torch.Tensor, lens, speed, *, out: Optional[torch.Tensor] = None, deltas: bool = False):
+    """Speaking rate on the rows of a padded batch (sopro_tsm_rows_f32, one-shot form): ``wav`` fp32 [rows, >= max(lens)] on the
+    device (rows ``wav.stride(0)`` apart, any pitch), ``lens`` valid samples per row, ``speed`` a float or one per row in [0.5, 2.0]
+    (> 1: faster, shorter) -> (out [rows, max(out_lens)], out_lens) with row b valid for out_lens[b] = tsm_out_len(lens[b], step_b)
+    samples.  One launch on the current stream and no synchronisation: the output lengths are host arithmetic.  ``out``: a
+    [rows, >= max(out_lens)] fp32 buffer to write into (nothing past a row's out_len is touched).  ``deltas=True`` (tests,
+    debugging) also returns the chosen offsets d_k per row as lists, and checks the lengths the device reports (one host copy)."""
+    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    rows = len(lens_h)
+    _tsm_check_rows(wav, lens_h, "time_stretch")
+    steps_h = tsm_steps(speed, rows)
+    out_lens_h = [tsm_out_len(n, s) for n, s in zip(lens_h, steps_h)]
+    cap = max(out_lens_h, default=0)
+    if out is None:
+        out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=wav.device)
+    else:
+        ptr(out)
+        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
+            raise SoproHipError(f"time_stretch: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+    if rows == 0:
+        return (out[:, :0], [], []) if deltas else (out[:, :0], [])
+    got_d, deltas_d, blocks_cap = _tsm_launch(wav, int(wav.shape[1]), lens_h, steps_h, None, True, out, deltas)
+    res = out[:, :cap]
+    if not deltas:
+        return res, out_lens_h
+    got = got_d.tolist()
+    if got != out_lens_h:
+        raise SoproHipError(f"time_stretch: the device reports lengths {got}, the host expected {out_lens_h}")
+    d = deltas_d.cpu().tolist()
+    return res, out_lens_h, [d[b][: tsm_blocks(out_lens_h[b])] for b in range(rows)]
+
+
+class TimeStretchState:
+    """Chunked form of ``time_stretch`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the blocks that became
+    ready, ``flush`` the rest.  Any chunking followed by ``flush`` gives the one-shot result bit for bit.  The state (block index,
+    last position, samples received, a retained tail of < 1920 samples per row) lives on the device; every call is one launch and
+    one small host copy (the lengths it produced)."""
+
+    def __init__(self, rows: int, speed, device):
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError("rows >= 1")
+        self.steps = tsm_steps(speed, self.rows)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise SoproHipError("TimeStretchState lives on a HIP device: the Sopro hot path has no CPU fallback")
+        self.state = torch.zeros(int(load().sopro_tsm_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
+
+    def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False, deltas: bool = False):
+        """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens[, deltas])."""
+        if wav is None:
+            n, lens_h = 0, [0] * self.rows
+        else:
+            n = int(wav.shape[-1])
+            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            _tsm_check_rows(wav, lens_h, "TimeStretchState.feed")
+        cap = int(load().sopro_tsm_chunk_out_cap(n))
+        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        got_d, deltas_d, _ = _tsm_launch(wav, n, lens_h, self.steps, self.state, flush, out, deltas)
+        got = got_d.tolist()
+        if min(got) < 0:
+            raise SoproHipError("TimeStretchState: a row's blocks did not fit the output buffer")
+        res = out[:, : max(got)]
+        if not deltas:
+            return res, got
+        d = deltas_d.cpu().tolist()
+        return res, got, [d[b][: tsm_blocks(got[b])] for b in range(self.rows)]
+
+    def flush(self, *, deltas: bool = False):
+        """The remaining blocks (zero extension, the last one cut at the row's total output length); the state is fresh afterwards."""
+        return self.feed(None, flush=True, deltas=deltas)
 
 
 def set_host_wait(blocking: bool, device=None) -> None:

@@ -118,6 +118,11 @@ def pause_samples(boundary: str, pauses_ms: Optional[Dict[str, float]] = None) -
     return int(round(ms * SAMPLE_RATE / 1000.0))
 
 
+def scaled_pause(samples: int, speed: float = 1.0) -> int:
+    """A pause at a speaking rate: int(round(samples / speed)) (``speed`` 1.0: unchanged)."""
+    return int(samples) if float(speed) == 1.0 else int(round(int(samples) / float(speed)))
+
+
 def group_plan(n: int, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32) -> List[int]:
     """How many consecutive segments go into each ``synthesize_batch`` call.  "throughput": ``max_rows`` per group, the remainder
     last.  "latency": 1, 2, 4, ... doubling up to ``max_rows``, then ``max_rows``, the remainder last (the first audio of a stream
@@ -175,21 +180,23 @@ class _Group(NamedTuple):
 
 
 def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top_p, temperature, anti_loop, style_strength, min_gen_frames,
-            seed, pauses_ms, join_kw) -> Iterator[_Group]:
+            seed, pauses_ms, join_kw, speed=1.0) -> Iterator[_Group]:
     """Run the groups in order: one ``synthesize_batch`` and one ``hip.join_segments`` each, straight from the decoder's padded
     batch.  Segment k of the text draws with nonce (seed + k) & 0xFFFFFFFF and row id 0 - the sampler stream
-    ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce."""
+    ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce.  ``speed``: the
+    batch comes back stretched (rows in parallel, before the join: trimming, fades and cue times then refer to the audio as it is
+    heard) and the pauses shrink or grow with it."""
     from . import hip
 
     n = len(segs)
     nonces = [(int(seed) + k) & 0xFFFFFFFF if seed is not None else tts.model.next_nonce(None) for k in range(n)]
-    gaps = [pause_samples(s.boundary, pauses_ms) for s in segs]
+    gaps = [scaled_pause(pause_samples(s.boundary, pauses_ms), speed) for s in segs]
     gaps[-1] = 0  # nothing follows the last segment
     k0 = 0
     for g in groups:
         batch = tts.synthesize_batch([s.text for s in segs[k0: k0 + g]], [ref] * g, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                      anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed,
-                                     nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True)
+                                     nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, speed=speed)
         piece, edges, offs = hip.join_segments(batch.wav, batch.lens, gaps[k0: k0 + g], **join_kw)
         yield _Group(k0, piece, edges, offs, batch)
         k0 += g
@@ -208,24 +215,27 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
-                    keep_parts: bool = False) -> LongformResult:
+                    keep_parts: bool = False, speed: float = 1.0) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``)."""
     import torch
 
+    from . import hip
+
+    hip.tsm_step(speed)  # (a rate out of range is refused before anything runs)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
         return LongformResult(torch.zeros(1, 1, 0, device=tts.device), [], [], [] if keep_parts else None, [] if keep_parts else None)
     pieces, cues, parts, all_edges, base = [], [], [], [], 0
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms)):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed):
         pieces.append(grp.piece)
         offs, edges = grp.offs.tolist(), grp.edges.tolist()
         for i, (s, e) in enumerate(edges):
             cues.append((segs[grp.first + i].text, base + offs[i], base + offs[i] + (e - s)))
             if keep_parts:
                 n = grp.batch.lens[i]
-                parts.append(LongformPart(grp.batch.wav[i, :n].reshape(1, 1, -1), grp.batch.tokens[i, : n // int(tts.codec.mc.frame_samples)]))
+                parts.append(LongformPart(grp.batch.wav[i, :n].reshape(1, 1, -1), grp.batch.tokens[i, : grp.batch.frames[i]]))
                 all_edges.append((s, e))
         base += offs[-1]
     wav = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).reshape(1, 1, -1)
@@ -236,12 +246,15 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True,
                 style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                 max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
-                fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32) -> Iterator[Any]:
+                fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0) -> Iterator[Any]:
     """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``)."""
+    from . import hip
+
+    hip.tsm_step(speed)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
         return
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms)):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed):
         yield grp.piece.reshape(1, -1)

@@ -24,7 +24,8 @@ class PaddedBatch(NamedTuple):
     """``synthesize_batch(..., padded=True)``: the decoder's batch where it is."""
     wav: torch.Tensor      # [B, T * 1920] fp32; row b is valid for lens[b] samples
     lens: List[int]        # samples
-    tokens: torch.Tensor   # [B, T, Q] int64; row b is valid for lens[b] / 1920 frames
+    tokens: torch.Tensor   # [B, T, Q] int64; row b is valid for frames[b] frames
+    frames: Optional[List[int]] = None  # frames per row (lens[b] / 1920 unless a speaking rate stretched ``wav``)
 
 
 class SoproTTS:
@@ -126,10 +127,14 @@ class SoproTTS:
                    ref_tokens_tq: Optional[torch.Tensor] = None, max_frames: int = 400, top_p: float = 0.9,
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
-                   seed: Optional[int] = None) -> torch.Tensor:
+                   seed: Optional[int] = None, speed: float = 1.0) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
-        draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75)."""
+        draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed`` (new): speaking rate
+        in [0.5, 2.0], applied to the decoded waveform by ``hip.time_stretch`` (pitch-preserving; 1.0 launches nothing)."""
+        from . import hip
+
+        step = hip.tsm_step(speed)
         text_ids = self.encode_text(text)
         if ref is None:
             ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
@@ -137,7 +142,11 @@ class SoproTTS:
             text_ids, ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
             style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
             min_gen_frames=min_gen_frames, seed=seed)
-        return self.codec.decode_full(tokens)
+        wav = self.codec.decode_full(tokens)
+        if step == hip.TSM_HS << 16 or wav.numel() == 0:
+            return wav
+        out, _ = hip.time_stretch(wav.reshape(1, -1), [int(wav.shape[-1])], speed)
+        return out.reshape(1, 1, -1)
 
     @torch.inference_mode()
     def synthesize_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, max_frames: int = 400,
@@ -145,16 +154,24 @@ class SoproTTS:
                          style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                          timings: Optional[Dict[str, float]] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                          phase_locks: Optional[tuple] = None, seed: Optional[int] = None, nonces: Optional[Sequence[int]] = None,
-                         row_ids: Optional[Sequence[int]] = None, padded: bool = False) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         row_ids: Optional[Sequence[int]] = None, padded: bool = False,
+                         speed: Union[float, Sequence[float]] = 1.0) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
         ``PaddedBatch`` of ``wav`` [B, T * 1920], ``lens`` (valid samples per row) and ``tokens`` [B, T, Q] (a copy: the engine's
-        own token matrix is overwritten by the next pass); the list above is ``[wav[b, :lens[b]].reshape(1, 1, -1)]``."""
+        own token matrix is overwritten by the next pass); the list above is ``[wav[b, :lens[b]].reshape(1, 1, -1)]``.
+        ``speed``: speaking rate in [0.5, 2.0], one float or one per row; the decoder's padded batch is stretched in one launch
+        on the bulk stream before it is sliced (``hip.time_stretch``), so ``PaddedBatch.wav`` / ``lens`` are the stretched rows
+        and ``tokens`` stay what the model produced.  All rows at 1.0: nothing is launched."""
         import contextlib
         import time
 
+        from . import hip
+
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
+        steps = hip.tsm_steps(speed, len(ids))
+        stretch = any(s != hip.TSM_HS << 16 for s in steps)
         locks = tuple(phase_locks) if phase_locks is not None else ()
         ar_lock = locks[0] if len(locks) > 0 else contextlib.nullcontext()
         bulk_lock = locks[1] if len(locks) > 1 else contextlib.nullcontext()
@@ -207,7 +224,7 @@ class SoproTTS:
             B, Tn = int(full.shape[0]), int(full.shape[1])
             if max(lens) == 0:
                 if padded:
-                    return PaddedBatch(torch.zeros(B, 0, device=self.device), [0] * B, torch.zeros(B, 0, self.model.Q, dtype=torch.long, device=self.device))
+                    return PaddedBatch(torch.zeros(B, 0, device=self.device), [0] * B, torch.zeros(B, 0, self.model.Q, dtype=torch.long, device=self.device), [0] * B)
                 return [torch.zeros(1, 1, 0, device=self.device) for _ in range(B)]
             # The padded batch goes to the decoder as it is: the decoder is causal, so the (valid, meaningless) codes a row holds
             # past its own length never reach the samples that are returned.
@@ -225,39 +242,46 @@ class SoproTTS:
                     timings["nar"] = timings.get("nar", 0.0) + (t1 - t0)
                     timings["mimi"] = timings.get("mimi", 0.0) + (time.perf_counter() - t1)
                 timings["_bulk_t1"] = time.perf_counter()
+            hop = int(self.codec.mc.frame_samples)
+            n_samples = [n * hop for n in lens]
+            if stretch:  # (rows at 1.0 in a mixed batch come back bit for bit: the operator is the identity there)
+                wav, n_samples = hip.time_stretch(wav, n_samples, speed)
             toks = None
             if padded:  # (the engine's own token matrix: copied before the next pass overwrites it, complete before any stream reads it)
                 toks = codes.long()
+            if padded or stretch:
                 self.model.bulk_stream.synchronize()
-        hop = int(self.codec.mc.frame_samples)
         if padded:
-            return PaddedBatch(wav, [n * hop for n in lens], toks)
-        return [wav[b, : lens[b] * hop].reshape(1, 1, -1) for b in range(B)]
+            return PaddedBatch(wav, n_samples, toks, lens)
+        return [wav[b, : n_samples[b]].reshape(1, 1, -1) for b in range(B)]
 
     def clone_lane(self) -> "SoproTTS":
         """Another engine over the same device weights (own streams / scratch), for pipelining batches."""
         return SoproTTS(self.model.clone_lane(), self.cfg, self.tokenizer, self.codec.clone_lane(), str(self.device))
 
-    def stream(self, text: str, **kwargs) -> Iterator[torch.Tensor]:
-        """reference: src/sopro/model.py:577-580"""
+    def stream(self, text: str, *, speed: float = 1.0, **kwargs) -> Iterator[torch.Tensor]:
+        """reference: src/sopro/model.py:577-580.  ``speed`` (new): speaking rate in [0.5, 2.0]; every decoded chunk goes through
+        the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream)."""
         from .streaming import stream
 
-        return stream(self, text, **kwargs)
+        return stream(self, text, speed=speed, **kwargs)
 
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
                      nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
-                     **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
+                     speed: float = 1.0, **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
-        entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch)."""
-        from .streaming import stream_batch
+        entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
+        A speaking rate is not available here (``speed`` other than 1.0 raises): use ``stream`` or ``synthesize_batch``."""
+        from .streaming import refuse_speed, stream_batch
 
+        refuse_speed(speed, "stream_batch")
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
-                            cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, **kwargs)
+                            cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, **kwargs)
 
-    def synthesize_long(self, text: str, **kwargs):
+    def synthesize_long(self, text: str, *, speed: float = 1.0, **kwargs):
         """New: a text of any length (a paragraph, an article, a chapter) -> ``LongformResult``: ``wav`` [1, 1, N] on the device and
         ``segments`` [(text, start sample, end sample)] in it.  The text is cut into sentences (``longform.split_text``,
         ``max_chars``), the voice is prepared once, groups of up to ``max_rows`` segments (``plan``: "throughput", "latency" or a
@@ -266,18 +290,20 @@ class SoproTTS:
         (``trim_db=None``: nothing is trimmed), pauses follow the kind of boundary (``pauses_ms``), cuts get ``fade_ms`` raised-cosine
         fades.  ``max_frames`` and the sampling parameters are per segment, as in ``synthesize``; segment k draws as
         ``synthesize(segment_k, ref=ref, seed=seed + k)`` does.  ``keep_parts=True`` also returns every segment's untrimmed
-        waveform and tokens (``parts``) and the kept range (``edges``).  Full parameter list: ``longform.synthesize_long``."""
+        waveform and tokens (``parts``) and the kept range (``edges``).  ``speed``: speaking rate in [0.5, 2.0]; every group's
+        padded batch is stretched before the join (``parts`` are the stretched rows, cue times refer to the stretched audio) and
+        the pauses are divided by it.  Full parameter list: ``longform.synthesize_long``."""
         from .longform import synthesize_long
 
-        return synthesize_long(self, text, **kwargs)
+        return synthesize_long(self, text, speed=speed, **kwargs)
 
-    def stream_long(self, text: str, **kwargs) -> Iterator[torch.Tensor]:
+    def stream_long(self, text: str, *, speed: float = 1.0, **kwargs) -> Iterator[torch.Tensor]:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
-        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit."""
+        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed``)."""
         from .longform import stream_long
 
-        return stream_long(self, text, **kwargs)
+        return stream_long(self, text, speed=speed, **kwargs)
 
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""

@@ -887,6 +887,34 @@ int sopro_tsm_rows_f32(const float* in, int64_t in_stride, const int32_t* in_len
                        int32_t flush, const float* tab, float* out, int64_t out_stride, int64_t out_cap, int32_t* out_lens, int32_t* deltas,
                        int32_t blocks_cap, void* stream);
 
+/* ---- word timestamps: attention maps of the AR text cross-attention and the best monotonic path through them -------------- */
+/* No reference counterpart (the reference never materialises attention weights).  Definition: DESIGN.md "Word timestamps";
+ * numpy / torch restatement: tests/align_ref.py.
+ * Scores.  Q [B][T_cap] rows of H heads x 96 columns (row t of utterance b at Q + b * q_bstride + t * ldq), K [B][S_cap] likewise,
+ * tlens / slens int32 [B] (clamped to the caps).  For t < tlens[b], s < slens[b] and every head h with bit h of head_mask set:
+ *   P_h[t, s] = softmax over s < slens[b] of (q_t,h . k_s,h * scale)      (fp32, fmaf chain over the 96 columns, expf)
+ *   v[t, s]   = sum_h weight * P_h[t, s]                                   (heads in ascending order)
+ *   mode 0: acc = v;  mode 1: acc += v;  mode 2: acc = logf(max(acc + v, 1e-9))
+ * acc [B][T_cap][ld_acc] fp32.  Nothing at t >= tlens[b] or s >= slens[b] is written.  One launch per attention layer (mode 0, 1, ...,
+ * 2 over the layers; head_mask 0 is allowed and contributes nothing), grid (B, frame tiles).  H <= 8, dh == 96, S_cap <= 2048.
+ * Path.  score [B][T_cap][ld] fp32 (finite), T = tlens[b], S = slens[b].  For T >= S >= 1:
+ *   D[0][0] = score[0][0], D[0][s > 0] = -inf;  D[t][s] = score[t][s] + max(D[t-1][s], D[t-1][s-1])  (D[.][-1] = -inf; one fp32 add)
+ *   backtrack from (T-1, S-1); a step goes to s - 1 only when D[t-1][s-1] > D[t-1][s] (ties stay)
+ *   path[b][t] = token of frame t;  bounds[b][s] = (first frame, last frame + 1) of token s;  total[b] = D[T-1][S-1];  status[b] = 0.
+ * Otherwise (T < S, T == 0 or S == 0): status[b] = 1, total[b] = 0, path[b][t] = (t * S) / T, bounds[b][s] = (f, f + hit) with
+ *   f = ceil(s * T / S) (0 when T == 0) and hit = 1 when frame f exists and maps to s.
+ * path int32 [B][path_ld], bounds int32 [B][S_cap][2], total float [B], status int32 [B]; nothing at t >= T or s >= S is written.
+ * ws: sopro_align_ws_bytes(B, T_cap, S_cap) bytes of device memory, 8-byte aligned (one backpointer bit per cell; 0: bad shape).
+ * One workgroup per utterance: S_cap <= 64 runs on one wave (D in a register per lane), S_cap <= 2048 on a double-buffered LDS row.
+ * Both enqueue one launch on `stream`, allocate nothing and synchronise nothing. */
+int64_t sopro_align_ws_bytes(int32_t B, int32_t T_cap, int32_t S_cap);
+int sopro_align_scores_f32(const float* Q, int64_t ldq, int64_t q_bstride, const float* K, int64_t ldk, int64_t k_bstride, const int32_t* tlens,
+                           const int32_t* slens, int32_t B, int32_t T_cap, int32_t S_cap, int32_t H, int32_t dh, float scale, uint32_t head_mask,
+                           float weight, int32_t mode, float* acc, int64_t ld_acc, int64_t acc_bstride, void* stream);
+int sopro_align_dp_f32(const float* score, int64_t ld, int64_t bstride, const int32_t* tlens, const int32_t* slens, int32_t B, int32_t T_cap,
+                       int32_t S_cap, void* ws, int64_t ws_bytes, int32_t* path, int64_t path_ld, int32_t* bounds, float* total, int32_t* status,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

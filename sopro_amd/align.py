@@ -1,0 +1,168 @@
+"""Word timestamps, host side: from a frame-to-token path (``SoproTTSModel.align_batch``) to word cues in samples.
+
+Pure Python, importable without a device.  The device half (attention maps of the AR generator's text cross-attention, the best
+monotonic path through them) is defined in DESIGN.md "Word timestamps" and include/sopro_hip.h.
+
+    Alignment   what the engine knows about one utterance, in frames
+    token_spans character range of every token id ``encode_text`` returns (BOS / EOS: empty)
+    word_cues   tokens -> words -> sample ranges
+    map_speed   a sample position before the speaking-rate stretch -> after it
+"""
+from __future__ import annotations
+
+import bisect
+import math
+from dataclasses import dataclass, field
+from typing import Any, List, NamedTuple, Optional, Sequence, Tuple
+
+HOP = 1920                      # samples per codec frame (24 kHz / 12.5 frames per second)
+TSM_HS, TSM_R = 480, 240        # the stretch's output hop and search radius (hip.TSM_HS / hip.TSM_R; kept here so that this module
+                                # imports without the kernel library)
+
+
+@dataclass
+class Alignment:
+    """One utterance's alignment, in frames, before any stretch.  ``path[t]``: the text position frame t belongs to;
+    ``token_frames[s]``: (first frame, last frame + 1) of text position s; ``total``: the path's log score; ``confidence`` =
+    exp(total / T), the geometric mean of the mean attention probability along the path (1 / S for flat maps); ``status`` 0: the
+    path is the best monotonic one, 1: no monotonic path exists (fewer frames than text positions, or none) and the frames were
+    spread evenly."""
+
+    path: List[int]
+    token_frames: List[Tuple[int, int]]
+    total: float
+    confidence: float = field(default=-1.0)
+    status: int = 0
+
+    def __post_init__(self):
+        if self.confidence < 0.0:
+            n = len(self.path)
+            self.confidence = math.exp(self.total / n) if (n > 0 and self.status == 0) else 0.0
+
+
+class WordCue(NamedTuple):
+    text: str
+    char_start: int
+    char_end: int
+    start_sample: int
+    end_sample: int
+
+
+class LongWordCue(NamedTuple):
+    """A word of ``synthesize_long``: character offsets are relative to segment ``segment``'s text, samples to the joined waveform."""
+    text: str
+    char_start: int
+    char_end: int
+    start_sample: int
+    end_sample: int
+    segment: int
+
+
+class TimedResult(NamedTuple):
+    wav: Any                    # [1, 1, N] on the device, what ``synthesize`` returns for the same seed
+    words: List[WordCue]
+    alignment: Alignment
+
+
+def token_spans(tokenizer: Any, text: str) -> List[Tuple[int, int]]:
+    """Character span (start, end) in ``text`` of every id ``tokenizer.encode(text)`` returns.  Sources, in this order: the
+    tokenizer's own ``encode_with_offsets(text) -> (ids, spans)``; a Hugging Face fast tokenizer under ``tokenizer.tok``
+    (``offset_mapping``; the BOS / EOS ids the wrapper adds get empty spans).  A tokenizer offering neither cannot be timed
+    automatically: pass ``token_spans=`` to the timed entry point."""
+    fn = getattr(tokenizer, "encode_with_offsets", None)
+    if fn is not None:
+        _ids, spans = fn(text)
+        return [(int(a), int(b)) for a, b in spans]
+    tok = getattr(tokenizer, "tok", None)
+    if tok is not None and getattr(tok, "is_fast", False):
+        enc = tok(text, add_special_tokens=False, return_offsets_mapping=True)
+        spans = [(int(a), int(b)) for a, b in enc["offset_mapping"]]
+        if getattr(tokenizer, "bos_id", None) is not None and getattr(tokenizer, "eos_id", None) is not None:
+            spans = [(0, 0)] + spans + [(len(text), len(text))]
+        return spans
+    raise TypeError("this tokenizer gives no character offsets (no encode_with_offsets, no fast Hugging Face tokenizer): "
+                    "pass token_spans=[(start, end), ...], one span per id of encode_text(text)")
+
+
+def words_of(text: str) -> List[Tuple[int, int]]:
+    """Maximal runs of non-whitespace characters as (start, end)."""
+    out, start = [], None
+    for i, ch in enumerate(text):
+        if ch.isspace():
+            if start is not None:
+                out.append((start, i))
+                start = None
+        elif start is None:
+            start = i
+    if start is not None:
+        out.append((start, len(text)))
+    return out
+
+
+def word_cues(text: str, spans: Sequence[Tuple[int, int]], token_frames: Sequence[Tuple[int, int]], hop: int = HOP) -> List[WordCue]:
+    """One cue per word of ``text``.  A token belongs to the word that contains the first non-blank character of its span; tokens
+    with empty (or all-blank) spans belong to no word - their frames are leading / trailing silence.  A word runs from the first
+    frame of its first token to the end frame of its last token, times ``hop``; a word with no token gets a zero-length cue at the
+    previous word's end (0 for the first word)."""
+    if len(spans) != len(token_frames):
+        raise ValueError(f"one span per token: {len(spans)} spans, {len(token_frames)} tokens")
+    words = words_of(text)
+    first: List[Optional[int]] = [None] * len(words)
+    last: List[Optional[int]] = [None] * len(words)
+    starts = [a for a, _b in words]
+    for s in range(len(spans)):
+        a, b = int(spans[s][0]), min(int(spans[s][1]), len(text))
+        c = max(a, 0)
+        while c < b and text[c].isspace():
+            c += 1
+        if c >= b:
+            continue
+        wi = bisect.bisect_right(starts, c) - 1  # (c is not blank, so it lies inside the word that starts at or before it)
+        if first[wi] is None:
+            first[wi] = s
+        last[wi] = s
+    cues: List[WordCue] = []
+    prev_end = 0
+    for k, (a, b) in enumerate(words):
+        if first[k] is None:
+            st = en = prev_end
+        else:
+            st, en = int(token_frames[first[k]][0]) * hop, int(token_frames[last[k]][1]) * hop
+        cues.append(WordCue(text[a:b], a, b, st, en))
+        prev_end = en
+    return cues
+
+
+def map_speed(sample: int, step: int) -> int:
+    """A sample position of the unstretched waveform -> its position after ``hip.time_stretch`` at ``step = hip.tsm_step(speed)``:
+    (sample * HS * 65536) // step, the arithmetic of ``hip.tsm_out_len``.  Exact for the waveform's length; inside it the stretch
+    places every 480-sample block within its search radius of the nominal position, so a cue is accurate to +-240 samples
+    (``TSM_R``, 10 ms) by the operator's definition."""
+    return (int(sample) * TSM_HS * 65536) // int(step)
+
+
+def stretch_cues(cues: Sequence[WordCue], step: int) -> List[WordCue]:
+    return [c._replace(start_sample=map_speed(c.start_sample, step), end_sample=map_speed(c.end_sample, step)) for c in cues]
+
+
+def long_cue(cue: WordCue, segment: int, off: int, edge_start: int, edge_end: int) -> LongWordCue:
+    """A segment's cue in the joined waveform: ``off + (sample - edge_start)``, the sample clamped to the kept range
+    [edge_start, edge_end] of the segment first (what the join trimmed away holds no word)."""
+    def m(v: int) -> int:
+        return int(off) + (min(max(int(v), int(edge_start)), int(edge_end)) - int(edge_start))
+
+    return LongWordCue(cue.text, cue.char_start, cue.char_end, m(cue.start_sample), m(cue.end_sample), int(segment))
+
+
+TIMING_KEYWORDS = ("alignment", "align_heads", "word_cues", "token_spans")
+
+
+def refuse_timing(kwargs, what: str) -> None:
+    """The streaming and serving paths have no word timing: a timing keyword there is an error, never ignored; timing
+    keywords that pass (None / False) are dropped from ``kwargs``."""
+    asked = [k for k in TIMING_KEYWORDS if kwargs.get(k) not in (None, False)]
+    if asked:
+        raise NotImplementedError(f"{what} has no word timing ({', '.join(asked)}): use synthesize_timed(), synthesize_batch(alignment=[...]) "
+                                  "or synthesize_long(word_cues=True)")
+    for k in TIMING_KEYWORDS:
+        kwargs.pop(k, None)

@@ -271,6 +271,10 @@ SYMBOLS = {
     "sopro_tsm_chunk_out_cap": (_i64, [_i64]),
     "sopro_tsm_state_bytes": (_i64, [_i32]),
     "sopro_tsm_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _i64, _i64, _p, _p, _i32, _p]),
+    "sopro_align_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "sopro_align_scores_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, C.c_uint32, _f32, _i32, _p, _i64,
+                                         _i64, _p]),
+    "sopro_align_dp_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _p, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1158,6 +1162,82 @@ class TimeStretchState:
     def flush(self, *, deltas: bool = False):
         """The remaining blocks (zero extension, the last one cut at the row's total output length); the state is fresh afterwards."""
         return self.feed(None, flush=True, deltas=deltas)
+
+
+# ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----
+ALIGN_S_MAX, ALIGN_DH = 2048, 96
+align_calls = 0  # launches of sopro_align_scores_f32 / sopro_align_dp_f32 by this process: a call that asks for no timing never adds to it
+
+
+def _align_lens(tlens, slens, B: int, dev):
+    """(tlens, slens) as int32 device vectors (host sequences are uploaded together)."""
+    if isinstance(tlens, torch.Tensor) and isinstance(slens, torch.Tensor):
+        return tlens.to(dev, torch.int32).contiguous(), slens.to(dev, torch.int32).contiguous()
+    th = [int(v) for v in (tlens.tolist() if isinstance(tlens, torch.Tensor) else tlens)]
+    sh = [int(v) for v in (slens.tolist() if isinstance(slens, torch.Tensor) else slens)]
+    if len(th) != B or len(sh) != B:
+        raise SoproHipError(f"one frame count and one text length per row ({B}), got {len(th)} and {len(sh)}")
+    both = torch.tensor([th, sh], dtype=torch.int32).to(dev)
+    return both[0], both[1]
+
+
+def align_scores(Q: torch.Tensor, K: torch.Tensor, tlens, slens, acc: torch.Tensor, *, head_mask: int, weight: float, mode: int,
+                 scale: Optional[float] = None, H: Optional[int] = None, ldq: Optional[int] = None, ldk: Optional[int] = None,
+                 q_bstride: Optional[int] = None, k_bstride: Optional[int] = None, q_off: int = 0, k_off: int = 0) -> None:
+    """One attention layer's share of the alignment scores (sopro_align_scores_f32): ``Q`` [B, T_cap, H * 96], ``K`` [B, S_cap, H * 96]
+    (or wider rows through ``ldq`` / ``ldk`` and element offsets), ``acc`` fp32 [B, T_cap, >= S_cap] with contiguous rows.  ``mode`` 0
+    writes the weighted sum of the heads in ``head_mask`` into ``acc``, 1 adds to it, 2 adds and finishes with log(max(acc, 1e-9))."""
+    global align_calls
+    ptr(acc)
+    if acc.dim() != 3 or acc.stride(2) != 1:
+        raise SoproHipError("align_scores: acc must be fp32 [B, T_cap, S_cap] with contiguous rows")
+    B, T_cap, S_cap = (int(v) for v in acc.shape)
+    H = int(H if H is not None else int(Q.shape[-1]) // ALIGN_DH)
+    ldq = int(Q.stride(-2) if ldq is None else ldq)
+    ldk = int(K.stride(-2) if ldk is None else ldk)
+    q_bstride = int((Q.stride(0) if Q.dim() == 3 else T_cap * ldq) if q_bstride is None else q_bstride)
+    k_bstride = int((K.stride(0) if K.dim() == 3 else S_cap * ldk) if k_bstride is None else k_bstride)
+    tl, sl = _align_lens(tlens, slens, B, acc.device)
+    align_calls += 1
+    _check(load().sopro_align_scores_f32(ptr(Q) + 4 * q_off, ldq, q_bstride, ptr(K) + 4 * k_off, ldk, k_bstride, ptr(tl, torch.int32),
+                                         ptr(sl, torch.int32), B, T_cap, S_cap, H, ALIGN_DH, float(scale if scale is not None else ALIGN_DH ** -0.5),
+                                         int(head_mask), float(weight), int(mode), ptr(acc), int(acc.stride(1)), int(acc.stride(0)), _stream()),
+           "sopro_align_scores_f32")
+
+
+def align_paths(score: torch.Tensor, tlens, slens, *, path: Optional[torch.Tensor] = None, bounds: Optional[torch.Tensor] = None,
+                total: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """The best monotonic path through each row's score matrix (sopro_align_dp_f32): ``score`` fp32 [B, T_cap, S_cap] on the device
+    (rows ``score.stride(1)`` apart, any pitch), ``tlens`` / ``slens`` frames and text positions per row -> (path int32 [B, T_cap],
+    bounds int32 [B, S_cap, 2] = (first frame, last frame + 1) per text position, total fp32 [B], status int32 [B]) on the device; entries
+    past a row's lengths are not written (given buffers keep what they held, fresh ones are zero).  One launch on the current stream."""
+    global align_calls
+    ptr(score)
+    if score.dim() != 3 or (int(score.shape[2]) > 1 and score.stride(2) != 1):
+        raise SoproHipError("align_paths: score must be fp32 [B, T_cap, S_cap] with contiguous rows")
+    B, T_cap, S_cap = (int(v) for v in score.shape)
+    if S_cap > ALIGN_S_MAX:
+        raise SoproHipError(f"align_paths: at most {ALIGN_S_MAX} text positions, got {S_cap}")
+    dev = score.device
+    lib = load()
+    with torch.cuda.device(dev):
+        tl, sl = _align_lens(tlens, slens, B, dev)
+        path = torch.zeros(B, T_cap, dtype=torch.int32, device=dev) if path is None else path
+        bounds = torch.zeros(B, S_cap, 2, dtype=torch.int32, device=dev) if bounds is None else bounds
+        total = torch.zeros(B, dtype=torch.float32, device=dev) if total is None else total
+        status = torch.zeros(B, dtype=torch.int32, device=dev) if status is None else status
+        if tuple(path.shape) != (B, T_cap) or path.stride(1) != 1 or tuple(bounds.shape) != (B, S_cap, 2) or not bounds.is_contiguous():
+            raise SoproHipError("align_paths: path must be int32 [B, T_cap] and bounds a contiguous int32 [B, S_cap, 2]")
+        need = int(lib.sopro_align_ws_bytes(B, T_cap, S_cap))
+        if ws is None:
+            ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        elif ws.numel() * ws.element_size() < need:
+            raise SoproHipError(f"align_paths: the workspace holds {ws.numel() * ws.element_size()} bytes, {need} are needed")
+        align_calls += 1
+        _check(lib.sopro_align_dp_f32(ptr(score), int(score.stride(1)), int(score.stride(0)), ptr(tl, torch.int32), ptr(sl, torch.int32), B, T_cap,
+                                      S_cap, ws.data_ptr(), int(ws.numel() * ws.element_size()), ptr(path, torch.int32), int(path.stride(0)),
+                                      ptr(bounds, torch.int32), ptr(total), ptr(status, torch.int32), _stream()), "sopro_align_dp_f32")
+    return path, bounds, total, status
 
 
 def set_host_wait(blocking: bool, device=None) -> None:

@@ -159,6 +159,7 @@ class LongformResult(NamedTuple):
     groups: List[int]                          # the group plan used
     parts: Optional[List[LongformPart]] = None  # keep_parts=True
     edges: Optional[List[Tuple[int, int]]] = None  # keep_parts=True: (start, end) the join kept of every part
+    words: Optional[List[Any]] = None          # word_cues=True: align.LongWordCue per word, samples in ``wav`` (accurate to one frame)
 
 
 def join_params(trim_db: Optional[float], keep_ms: float, fade_ms: float) -> Dict[str, Any]:
@@ -177,10 +178,11 @@ class _Group(NamedTuple):
     edges: Any      # host int32 [g, 2]
     offs: Any       # host int64 [g + 1]
     batch: Any      # tts.PaddedBatch
+    align: Any = None  # word_cues: one align.Alignment per row
 
 
 def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top_p, temperature, anti_loop, style_strength, min_gen_frames,
-            seed, pauses_ms, join_kw, speed=1.0) -> Iterator[_Group]:
+            seed, pauses_ms, join_kw, speed=1.0, word_cues=False, align_heads=None) -> Iterator[_Group]:
     """Run the groups in order: one ``synthesize_batch`` and one ``hip.join_segments`` each, straight from the decoder's padded
     batch.  Segment k of the text draws with nonce (seed + k) & 0xFFFFFFFF and row id 0 - the sampler stream
     ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce.  ``speed``: the
@@ -194,11 +196,13 @@ def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top
     gaps[-1] = 0  # nothing follows the last segment
     k0 = 0
     for g in groups:
+        sink = [] if word_cues else None  # (None: the pass launches nothing for timing)
         batch = tts.synthesize_batch([s.text for s in segs[k0: k0 + g]], [ref] * g, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                      anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed,
-                                     nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, speed=speed)
+                                     nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, speed=speed, alignment=sink,
+                                     align_heads=align_heads)
         piece, edges, offs = hip.join_segments(batch.wav, batch.lens, gaps[k0: k0 + g], **join_kw)
-        yield _Group(k0, piece, edges, offs, batch)
+        yield _Group(k0, piece, edges, offs, batch, sink)
         k0 += g
 
 
@@ -215,31 +219,49 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
-                    keep_parts: bool = False, speed: float = 1.0) -> LongformResult:
-    """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``)."""
+                    keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None) -> LongformResult:
+    """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
+    ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
+    (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k; at a ``speed`` other than 1.0 the
+    cue goes through ``align.map_speed`` first).  ``token_spans``: a callable text -> [(start, end)] per token id for tokenizers
+    that give no character offsets; ``align_heads``: the (layer, head) pairs to average."""
     import torch
 
+    from . import align as A
     from . import hip
 
-    hip.tsm_step(speed)  # (a rate out of range is refused before anything runs)
+    step = hip.tsm_step(speed)  # (a rate out of range is refused before anything runs)
+    if token_spans is not None and not callable(token_spans):
+        raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
+    spans_of = token_spans if token_spans is not None else (lambda t: A.token_spans(tts.tokenizer, t))
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
-        return LongformResult(torch.zeros(1, 1, 0, device=tts.device), [], [], [] if keep_parts else None, [] if keep_parts else None)
+        return LongformResult(torch.zeros(1, 1, 0, device=tts.device), [], [], [] if keep_parts else None, [] if keep_parts else None,
+                              [] if word_cues else None)
+    if word_cues:
+        spans_of(segs[0].text)  # (a tokenizer without character offsets is refused before any segment runs)
     pieces, cues, parts, all_edges, base = [], [], [], [], 0
+    words = [] if word_cues else None
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, word_cues=word_cues, align_heads=align_heads):
         pieces.append(grp.piece)
         offs, edges = grp.offs.tolist(), grp.edges.tolist()
         for i, (s, e) in enumerate(edges):
             cues.append((segs[grp.first + i].text, base + offs[i], base + offs[i] + (e - s)))
+            if word_cues:
+                seg_text = segs[grp.first + i].text
+                wc = A.word_cues(seg_text, spans_of(seg_text), grp.align[i].token_frames)
+                if step != hip.TSM_HS << 16:
+                    wc = A.stretch_cues(wc, step)
+                words.extend(A.long_cue(c, grp.first + i, base + offs[i], s, e) for c in wc)
             if keep_parts:
                 n = grp.batch.lens[i]
                 parts.append(LongformPart(grp.batch.wav[i, :n].reshape(1, 1, -1), grp.batch.tokens[i, : grp.batch.frames[i]]))
                 all_edges.append((s, e))
         base += offs[-1]
     wav = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).reshape(1, 1, -1)
-    return LongformResult(wav, cues, groups, parts if keep_parts else None, all_edges if keep_parts else None)
+    return LongformResult(wav, cues, groups, parts if keep_parts else None, all_edges if keep_parts else None, words)
 
 
 def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = None, ref_tokens_tq=None, ref_seconds: Optional[float] = None,

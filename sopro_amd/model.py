@@ -632,13 +632,17 @@ class SoproTTSModel:
     def generate_tokens_batch(self, ids_list: Sequence[torch.Tensor], refs: Sequence[PreparedReference], *, max_frames: int,
                               top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True,
                               style_strength: float = 1.0, min_gen_frames: Optional[int] = None,
-                              timings: Optional[Dict[str, float]] = None, seed: Optional[int] = None) -> List[torch.Tensor]:
-        """B utterances -> list of [T_b, Q] int64 token matrices (new, batched form of generate_tokens)."""
+                              timings: Optional[Dict[str, float]] = None, seed: Optional[int] = None, alignment: Optional[list] = None,
+                              align_heads=None) -> List[torch.Tensor]:
+        """B utterances -> list of [T_b, Q] int64 token matrices (new, batched form of generate_tokens).  ``alignment``: a list
+        that receives one ``Alignment`` per row (align_batch); ``None`` launches nothing for it."""
         ev = _PhaseTimer(self.stream, timings)
         state = self.phase_ar(ids_list, refs, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                               style_strength=style_strength, min_gen_frames=min_gen_frames, ev=ev, seed=seed)
         toks = self.phase_nar(state)
         ev.mark("nar")
+        if alignment is not None:
+            alignment[:] = self.align_batch(state["prep"], state, heads=align_heads)
         return toks
 
     def plan_for(self, ids_list, max_frames: int) -> "_ARPlan":
@@ -678,7 +682,8 @@ class SoproTTSModel:
                                             min_gen_frames=min_gen_frames, seed=seed, run=run, inplace=inplace)
         if ev is not None:
             ev.mark("ar")
-        return {"cond_ar": prep["cond_ar"], "hist": hist, "lens": lens, "B": len(ids_list), "plan": run.plan if inplace else None}
+        return {"cond_ar": prep["cond_ar"], "hist": hist, "lens": lens, "B": len(ids_list), "plan": run.plan if inplace else None,
+                "prep": prep}  # (the conditioning this phase ran on: what align_batch replays the stack against)
 
     def phase_nar(self, state, full: bool = False, sync: bool = True, raw: bool = False):
         """Throughput-bound half: NAR refinement of the generated codebook-0 tokens -> one [T_b, Q] matrix per utterance, or with
@@ -704,6 +709,128 @@ class SoproTTSModel:
         if full:
             return toks
         return [toks[b, : lens[b]] for b in range(B)]
+
+    # ------------------------------------------------------------------ word timestamps
+    def _align_operands(self) -> Dict[str, Any]:
+        """The AR stack's weights in the layouts of the full-sequence operators (made once, at the first timed call): the GLU
+        projection packed per 64 rows as the contraction's gating epilogue reads it (pack.pack_glu; the engine keeps the natural
+        layout for the frame kernels), everything else as it is.  The RMSNorm weights are folded into the projections that follow
+        (pack.py), so the norms of the replay run with a vector of ones."""
+        ops = getattr(self, "_align_ops", None)
+        if ops is None:
+            from .pack import pack_glu
+
+            w, dev = self.w, self.device
+            ops = {"ones": torch.ones(self.D, device=dev), "col": _i32([0], dev), "off": _i32([0], dev), "wq": torch.ones(1, device=dev)}
+            for i in range(len(self.cfg.ar_dilations)):
+                ops[f"glu.{i}"] = tuple(t.contiguous() for t in pack_glu(w[f"ar.blocks.{i}.glu.w"], w[f"ar.blocks.{i}.glu.b"]))
+            self._align_ops = ops  # (shared by the lanes of clone_lane: read-only)
+        return ops
+
+    def _align_heads(self, heads) -> Dict[int, int]:
+        """(layer, head) pairs -> head mask per attention layer; ``None``: every head of every layer."""
+        layers = tuple(int(i) for i in self.cfg.ar_xattn_layers)
+        if heads is None:
+            return {i: 0xF for i in layers}
+        masks = {i: 0 for i in layers}
+        for pair in heads:
+            try:
+                l, h = (int(v) for v in pair)
+            except (TypeError, ValueError):
+                raise ValueError(f"align_heads wants (layer, head) pairs, got {pair!r}") from None
+            if l not in masks or not 0 <= h < 4:
+                raise ValueError(f"align_heads: layer must be one of {layers} and head in [0, 4), got {(l, h)}")
+            masks[l] |= 1 << h
+        if not any(masks.values()):
+            raise ValueError("align_heads selects no head")
+        return masks
+
+    @torch.inference_mode()
+    def align_batch(self, prep: Dict[str, Any], state: Dict[str, Any], heads=None) -> List["Alignment"]:
+        """Word timing's device half, a post-pass over a finished AR phase (DESIGN.md "Word timestamps"): the AR stack is replayed
+        teacher-forced over all frames at once on the generated codebook-0 tokens (oracle ``ar_forward_teacher`` without the head),
+        ``sopro_align_scores_f32`` turns the three cross-attention layers' queries and keys into log mean attention, and
+        ``sopro_align_dp_f32`` finds each row's best monotonic path -> one ``Alignment`` per row, in frames.  Runs on the bulk stream;
+        ``prep`` (conditioning: ``txt_seq``, ``text_lens``, ``text_lens_host``) and ``state`` (phase_ar: ``cond_ar``, ``hist``,
+        ``lens``) are only read.  ``heads``: the (layer, head) pairs to average, default all 12.  The score matrix of the last call
+        stays in ``self.align_last`` ([B, T, S] on the device, valid until the next call)."""
+        from .align import Alignment
+
+        cfg, w, dev, D = self.cfg, self.w, self.device, self.D
+        masks = self._align_heads(heads)
+        n_sel = sum(bin(v).count("1") for v in masks.values())
+        lens_t = [int(n) for n in state["lens"]]
+        lens_s = [int(n) for n in prep["text_lens_host"]]
+        B, S = int(state["B"]), int(prep["txt_seq"].shape[1])
+        hist, cond = state["hist"], state["cond_ar"]
+        Tp = min(max(8, -(-max(lens_t) // 8) * 8), int(hist.shape[1]), int(cond.shape[1]))
+        M = B * Tp
+        ops = self._align_operands()
+        ksz = int(cfg.ar_kernel)
+        layers = [int(i) for i in cfg.ar_xattn_layers]
+        last = max(i for i in layers if masks[i])  # nothing after this layer's queries is needed
+        modes = {i: (0 if n == 0 else (2 if n == len(layers) - 1 else 1)) for n, i in enumerate(layers)}
+        get = self.ws.get
+        with self.on_stream(bulk=True):
+            lens_d = torch.tensor([lens_t, lens_s], dtype=torch.int32).to(dev)
+            tl, sl = lens_d[0], lens_d[1]
+            tok = get("align.tok", (B, Tp), dtype=torch.int32)
+            tok[:, 0] = int(cfg.bos_row)
+            if Tp > 1:
+                tok[:, 1:] = hist[:, : Tp - 1].clamp(0, self.V - 1)  # (codes past a row's own length are never used: the stack is causal)
+            xa, xb, nb = get("align.xa", (M, D)), get("align.xb", (M, D)), get("align.n", (M, D))
+            g, f = get("align.g", (M, D)), get("align.f", (M, 4 * D))
+            xb.view(B, Tp, D).copy_(cond[:, :Tp])
+            hip.codebook_sum(tok, 1, ops["col"], ops["off"], ops["wq"], w["cb_embed"], xa, rows=M, D=D, base=xb, alpha=1.0, beta=1.0)
+            acc = get("align.acc", (B, Tp, S))
+            x, y = xa, xb
+            ts = prep["txt_seq"].to(dev).float().contiguous().view(B * S, D)
+            nkv, kv = get("align.nkv", (B * S, D)), get("align.kv", (B * S, 2 * D))
+            q, att = get("align.q", (M, D)), get("align.att", (M, D))
+            for i, dil in enumerate(cfg.ar_dilations):
+                p = f"ar.blocks.{i}"
+                gw, gb = ops[f"glu.{i}"]
+                hip.norm(x, nb, ops["ones"], rows=M, C_=D, eps=RMS_EPS)
+                hip.gemm(nb, gw, g, M=M, N=2 * D, K=D, bias=gb, epilogue=hip.EPI_GLU)
+                hip.dwconv(g, w[p + ".dw.w"], w[p + ".dw.b"], y, B=B, T=Tp, C_=D, ksize=ksz, dil=int(dil), left=(ksz - 1) * int(dil), mode=1, res=x)
+                hip.norm(y, nb, ops["ones"], rows=M, C_=D, eps=RMS_EPS)
+                hip.gemm(nb, w[p + ".ff1.w"], f, M=M, N=4 * D, K=D, bias=w[p + ".ff1.b"], epilogue=hip.EPI_GELU)
+                hip.gemm(f, w[p + ".ff2.w"], x, M=M, N=D, K=4 * D, bias=w[p + ".ff2.b"], epilogue=hip.EPI_RES, R=y)
+                if i not in masks:
+                    continue
+                pa = f"ar.x_attns.{i}"
+                hip.norm(ts, nkv, w[pa + ".nkv.weight"], rows=B * S, C_=D, eps=RMS_EPS)
+                hip.gemm(nkv, w[pa + ".kv.w"], kv, M=B * S, N=2 * D, K=D)
+                hip.norm(x, nb, ops["ones"], rows=M, C_=D, eps=RMS_EPS)
+                hip.gemm(nb, w[pa + ".qa.w"], q, M=M, N=D, K=D)  # (qa.w = q_proj with RMSNorm_nq's weight folded in)
+                hip.align_scores(q, kv, tl, sl, acc, head_mask=masks[i], weight=1.0 / n_sel, mode=modes[i], H=4, ldq=D, ldk=2 * D,
+                                 q_bstride=Tp * D, k_bstride=S * 2 * D)
+                if i == last:
+                    break
+                hip.attention(q, kv, kv, att, B=B, H=4, dh=D // 4, Tq=Tp, Tk=S, ldq=D, ldk=2 * D, ldv=2 * D, ldo=D, q_bstride=Tp * D,
+                              k_bstride=S * 2 * D, v_bstride=S * 2 * D, o_bstride=Tp * D, klens=sl, v_off=D)
+                hip.gemm(att, w[pa + ".o.w"], y, M=M, N=D, K=D, epilogue=hip.EPI_RES, R=x, scale=w[pa + ".gate_scale"])
+                x, y = y, x
+            for i in layers:  # the layers past the last selected one add nothing; the last launch still finishes the scores
+                if i > last:
+                    hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=modes[i], H=4, ldq=D, ldk=2 * D, q_bstride=Tp * D,
+                                     k_bstride=S * 2 * D)
+            if len(layers) == 1:  # (one attention layer: its launch wrote the sum, a second one finishes it)
+                hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=2, H=4, ldq=D, ldk=2 * D, q_bstride=Tp * D, k_bstride=S * 2 * D)
+            dws = get("align.dp_ws", (max(1, int(hip.load().sopro_align_ws_bytes(B, Tp, S)) // 8),), dtype=torch.int64)
+            out = get("align.out", (B * Tp + B * S * 2 + 2 * B,), dtype=torch.int32)  # path | bounds | total | status: one download
+            out.zero_()
+            path, bounds = out[: B * Tp].view(B, Tp), out[B * Tp: B * Tp + 2 * B * S].view(B, S, 2)
+            total, status = out[B * Tp + 2 * B * S: B * Tp + 2 * B * S + B].view(torch.float32), out[B * Tp + 2 * B * S + B:]
+            hip.align_paths(acc, tl, sl, path=path, bounds=bounds, total=total, status=status, ws=dws)
+            host = out.cpu()
+        self.align_last = acc
+        hp = host[: B * Tp].view(B, Tp).tolist()
+        hb = host[B * Tp: B * Tp + 2 * B * S].view(B, S, 2).tolist()
+        ht = host[B * Tp + 2 * B * S: B * Tp + 2 * B * S + B].view(torch.float32).tolist()
+        hs = host[B * Tp + 2 * B * S + B:].tolist()
+        return [Alignment(path=hp[b][: lens_t[b]], token_frames=[tuple(v) for v in hb[b][: lens_s[b]]], total=float(ht[b]), status=int(hs[b]))
+                for b in range(B)]
 
 
 class _PhaseTimer:

@@ -117,13 +117,18 @@ class SynthesisService:
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
                anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
-               text_ids: Optional[torch.Tensor] = None, speed: float = 1.0) -> "Future[torch.Tensor]":
+               text_ids: Optional[torch.Tensor] = None, speed: float = 1.0, **timing) -> "Future[torch.Tensor]":
         """Queue one utterance; the future resolves to the waveform ``[1, 1, N]`` on the device (``synthesize``'s result).
         ``speed``: speaking rate in [0.5, 2.0] of this request (``mode="batch"`` only).  It is applied to the decoded batch, one
-        rate per row, so requests with different rates share a batch."""
+        rate per row, so requests with different rates share a batch.  The service has no word timing in either mode: a timing
+        keyword (``alignment``, ``word_cues``, ...) raises."""
         from . import hip
+        from .align import refuse_timing
         from .streaming import refuse_speed
 
+        refuse_timing(timing, f"SynthesisService(mode={'continuous' if self.engine is not None else 'batch'!r})")
+        if timing:
+            raise TypeError(f"submit() got unexpected keyword arguments {sorted(timing)}")
         if self._closed:
             raise RuntimeError("service is closed")
         hip.tsm_step(speed)

@@ -3,8 +3,9 @@
 Same constructor / method signatures and error behaviour as the reference class, so existing call
 sites (``README.md:69-120``, ``src/sopro/cli.py``, ``demo/server.py:224,241``) keep working; the body
 of every method runs on the MI355X engine (``sopro_amd.model`` / ``sopro_amd.codec``).  Additions
-that the reference does not have: ``synthesize_batch``, ``stream_batch``, ``from_weights`` and the long-form entry points
-``synthesize_long`` / ``stream_long`` (text of any length: split, batched, joined on the device; ``sopro_amd.longform``).
+that the reference does not have: ``synthesize_batch``, ``stream_batch``, ``from_weights``, the long-form entry points
+``synthesize_long`` / ``stream_long`` (text of any length: split, batched, joined on the device; ``sopro_amd.longform``) and
+``synthesize_timed`` (word timestamps; ``sopro_amd.align``).
 """
 from __future__ import annotations
 
@@ -155,7 +156,8 @@ class SoproTTS:
                          timings: Optional[Dict[str, float]] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                          phase_locks: Optional[tuple] = None, seed: Optional[int] = None, nonces: Optional[Sequence[int]] = None,
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
-                         speed: Union[float, Sequence[float]] = 1.0) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
+                         align_heads=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
@@ -163,7 +165,11 @@ class SoproTTS:
         own token matrix is overwritten by the next pass); the list above is ``[wav[b, :lens[b]].reshape(1, 1, -1)]``.
         ``speed``: speaking rate in [0.5, 2.0], one float or one per row; the decoder's padded batch is stretched in one launch
         on the bulk stream before it is sliced (``hip.time_stretch``), so ``PaddedBatch.wav`` / ``lens`` are the stretched rows
-        and ``tokens`` stay what the model produced.  All rows at 1.0: nothing is launched."""
+        and ``tokens`` stay what the model produced.  All rows at 1.0: nothing is launched.
+        ``alignment``: a sink like ``timings`` - a list passed in is filled with one ``align.Alignment`` per row (frame -> text
+        position path, frame range per position, confidence; in frames, before any stretch) by a post-pass on the bulk stream
+        (``model.align_batch``: the AR stack replayed over the generated tokens, ``hip.align_scores`` / ``hip.align_paths``);
+        ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched."""
         import contextlib
         import time
 
@@ -172,6 +178,8 @@ class SoproTTS:
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
         steps = hip.tsm_steps(speed, len(ids))
         stretch = any(s != hip.TSM_HS << 16 for s in steps)
+        if alignment is not None:
+            self.model._align_heads(align_heads)  # (a bad selection is refused before anything runs)
         locks = tuple(phase_locks) if phase_locks is not None else ()
         ar_lock = locks[0] if len(locks) > 0 else contextlib.nullcontext()
         bulk_lock = locks[1] if len(locks) > 1 else contextlib.nullcontext()
@@ -223,6 +231,8 @@ class SoproTTS:
             lens = [int(n) for n in state["lens"]]
             B, Tn = int(full.shape[0]), int(full.shape[1])
             if max(lens) == 0:
+                if alignment is not None:
+                    alignment[:] = self.model.align_batch(state["prep"], state, heads=align_heads)
                 if padded:
                     return PaddedBatch(torch.zeros(B, 0, device=self.device), [0] * B, torch.zeros(B, 0, self.model.Q, dtype=torch.long, device=self.device), [0] * B)
                 return [torch.zeros(1, 1, 0, device=self.device) for _ in range(B)]
@@ -242,6 +252,8 @@ class SoproTTS:
                     timings["nar"] = timings.get("nar", 0.0) + (t1 - t0)
                     timings["mimi"] = timings.get("mimi", 0.0) + (time.perf_counter() - t1)
                 timings["_bulk_t1"] = time.perf_counter()
+            if alignment is not None:  # (queued behind the decoder on the bulk stream)
+                alignment[:] = self.model.align_batch(state["prep"], state, heads=align_heads)
             hop = int(self.codec.mc.frame_samples)
             n_samples = [n * hop for n in lens]
             if stretch:  # (rows at 1.0 in a mixed batch come back bit for bit: the operator is the identity there)
@@ -255,6 +267,42 @@ class SoproTTS:
             return PaddedBatch(wav, n_samples, toks, lens)
         return [wav[b, : n_samples[b]].reshape(1, 1, -1) for b in range(B)]
 
+    @torch.inference_mode()
+    def synthesize_timed(self, text: str, *, ref: Optional[PreparedReference] = None, ref_audio_path: Optional[str] = None,
+                         ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
+                         top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
+                         ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
+                         speed: float = 1.0):
+        """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
+        returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
+        ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
+        ``align.Alignment`` with its ``confidence``.  Cues are whole frames (1920 samples); with ``speed`` other than 1.0 they are
+        mapped by ``align.map_speed`` (accurate to +-240 samples, the stretch's search radius).  ``token_spans``: the character span
+        of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
+        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12)."""
+        from . import align as A
+        from . import hip
+
+        step = hip.tsm_step(speed)
+        text_ids = self.encode_text(text)
+        spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
+        if len(spans) != int(text_ids.numel()):
+            raise ValueError(f"token_spans: {len(spans)} spans for {int(text_ids.numel())} token ids")
+        if ref is None:
+            ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
+        sink: list = []
+        tokens = self.model.generate_tokens_batch(
+            [text_ids], [ref], max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
+            style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
+            min_gen_frames=min_gen_frames, seed=seed, alignment=sink, align_heads=align_heads)[0]
+        wav = self.codec.decode_full(tokens)
+        words = A.word_cues(text, spans, sink[0].token_frames, hop=int(self.codec.mc.frame_samples))
+        if step != hip.TSM_HS << 16 and wav.numel() > 0:
+            out, _ = hip.time_stretch(wav.reshape(1, -1), [int(wav.shape[-1])], speed)
+            wav = out.reshape(1, 1, -1)
+            words = A.stretch_cues(words, step)
+        return A.TimedResult(wav, words, sink[0])
+
     def clone_lane(self) -> "SoproTTS":
         """Another engine over the same device weights (own streams / scratch), for pipelining batches."""
         return SoproTTS(self.model.clone_lane(), self.cfg, self.tokenizer, self.codec.clone_lane(), str(self.device))
@@ -262,8 +310,10 @@ class SoproTTS:
     def stream(self, text: str, *, speed: float = 1.0, **kwargs) -> Iterator[torch.Tensor]:
         """reference: src/sopro/model.py:577-580.  ``speed`` (new): speaking rate in [0.5, 2.0]; every decoded chunk goes through
         the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream)."""
+        from .align import refuse_timing
         from .streaming import stream
 
+        refuse_timing(kwargs, "stream")
         return stream(self, text, speed=speed, **kwargs)
 
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
@@ -274,8 +324,10 @@ class SoproTTS:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
         entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
         A speaking rate is not available here (``speed`` other than 1.0 raises): use ``stream`` or ``synthesize_batch``."""
+        from .align import refuse_timing
         from .streaming import refuse_speed, stream_batch
 
+        refuse_timing(kwargs, "stream_batch")
         refuse_speed(speed, "stream_batch")
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
@@ -292,7 +344,8 @@ class SoproTTS:
         ``synthesize(segment_k, ref=ref, seed=seed + k)`` does.  ``keep_parts=True`` also returns every segment's untrimmed
         waveform and tokens (``parts``) and the kept range (``edges``).  ``speed``: speaking rate in [0.5, 2.0]; every group's
         padded batch is stretched before the join (``parts`` are the stretched rows, cue times refer to the stretched audio) and
-        the pauses are divided by it.  Full parameter list: ``longform.synthesize_long``."""
+        the pauses are divided by it.  ``word_cues=True`` also fills ``words`` (one ``align.LongWordCue`` per word, samples in the
+        joined waveform).  Full parameter list: ``longform.synthesize_long``."""
         from .longform import synthesize_long
 
         return synthesize_long(self, text, speed=speed, **kwargs)
@@ -301,8 +354,10 @@ class SoproTTS:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
         segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed``)."""
+        from .align import refuse_timing
         from .longform import stream_long
 
+        refuse_timing(kwargs, "stream_long")
         return stream_long(self, text, speed=speed, **kwargs)
 
     def save_wav(self, path: str, wav: torch.Tensor) -> None:

@@ -887,6 +887,55 @@ int sopro_tsm_rows_f32(const float* in, int64_t in_stride, const int32_t* in_len
                        int32_t flush, const float* tab, float* out, int64_t out_stride, int64_t out_cap, int32_t* out_lens, int32_t* deltas,
                        int32_t blocks_cap, void* stream);
 
+/* ---- pitch: band-limited resampling of the rows of a padded batch at an arbitrary ratio per row --------------------------- */
+/* The model has no pitch input either, so a pitch shift by the ratio rho is applied to the decoded waveform: a stretch by rho
+ * (sopro_tsm_rows_f32 at speed / rho) followed by this resampler, which reads rho times as fast.  The duration comes back and
+ * every frequency - formants included: this is no formant-preserving shifter - is multiplied by rho.  No reference counterpart.
+ * 24 kHz mono fp32.  Every product and sum below is a separately rounded fp32 operation (no contraction) in a fixed order and the
+ * library evaluates no transcendental function (the host makes the filter bank, as it makes the fade table): the operator has one
+ * right answer, bit for bit (tests/pitch_ref.py restates it in numpy).
+ *   NT = 64 taps, P = 256 phases, HALF = 32.
+ *   inc = round(2^(semitones / 12) * 2^32): all the device sees of a pitch, clamped to [2^31, 2^33] (+-12 semitones); rho = inc / 2^32.
+ *   Bank of an inc: float [P + 1][NT], made by the host in float64 and cast to fp32.  fc = 0.5 min(1, 2^32 / inc) - 0.034 cycles
+ *     per input sample; t = j - 31 - p / 256 for row p in 0..256 and tap j in 0..63; w(t) = I0(7 sqrt(1 - (t / 32)^2)) / I0(7) for
+ *     |t| < 32, else 0 (a Kaiser window, beta = 7); g = 2 fc sinc(2 fc t) w(t) with sinc(u) = sin(pi u) / (pi u); every row is
+ *     divided by its own float64 sum (DC gain 1).  Row 256 is phase 1.0: row 0 moved by one tap, up to the normalisation.  The
+ *     band above fc is removed.  Every inc <= 2^32 has the same bank.
+ *   x[0 .. L) is a row; reads below 0 or at or past L give 0.0 (nothing past a row's length is read from memory).  L <= 2^30.
+ *   M = (L << 32) / inc output samples (integer division in int64).
+ *   Sample n: pos = n * inc (uint64, Q32); i = pos >> 32; fr = pos & 0xFFFFFFFF; p = fr >> 24; f = fl32(fr & 0xFFFFFF) * 2^-24
+ *     (exact).  With acc = 0.0f, for j = 0 .. 63 in ascending order: h0 = bank[p][j], h1 = bank[p + 1][j],
+ *     c = fl32(h0 + fl32(f * fl32(h1 - h0))), acc = fl32(acc + fl32(c * x[i - 31 + j])).  y[n] = acc.
+ *   Identity: a row with inc == 2^32 is a copy, y[n] = x[n], and the bank is not read: rows at pitch 0 in a mixed batch come back
+ *     bit for bit.
+ * Chunked form (same numbers): `state` holds, per row, (next output index, samples received, the retained input tail).  A call
+ * appends in[row, 0 .. in_lens[row]) to the row and computes every output n with i_n + 32 < received (all of its taps are in, so
+ * it lies below the final M whatever follows); identity rows follow the same rule.  With `flush` the rest is computed with zero
+ * extension up to M of the total length and the row's state is zeroed (a fresh row).  Any chunking followed by a flush gives the
+ * one-shot result bit for bit.  The retained tail is everything from i_next - 31 on, i_next the position of the first output not
+ * yet computed: that output was not ready, so i_next + 32 >= received and the tail holds received - (i_next - 31) <= 63 samples:
+ * fewer than 64 <= SOPRO_PITCH_TAIL.
+ * Output of a call: out[row, 0 .. out_lens[row]) = the outputs computed by THIS call, in order (one-shot: the whole y).  Nothing at
+ * or past out_cap or past out_lens[row] is written; a row whose outputs do not fit gets out_lens[row] = -1, nothing written and a
+ * zeroed state (a sizing error of the caller: sopro_pitch_out_len gives the exact one-shot size, sopro_pitch_chunk_out_cap(in_cap)
+ * = 2 (in_cap + 64) + 2 a bound for one chunked call, flush included).
+ * incs int64 [rows], bank_idx int32 [rows] (clamped to [0, n_banks)) into banks float [n_banks][257][64] (16-byte aligned),
+ * in_lens int32 [rows] (clamped to [0, in_cap]), out_lens int32 [rows]: device memory.  state: NULL for a one-shot call (flush must
+ * be set), else sopro_pitch_state_bytes(rows) bytes of device memory, zeroed before a row's first chunk.  Rows need no alignment
+ * beyond 4 bytes.  sopro_pitch_rows_f32 enqueues one launch over (row, tile of SOPRO_PITCH_TILE outputs) - with a state a second,
+ * small one that updates it after every tile has read the tail - on `stream`, allocates nothing and synchronises nothing; the
+ * helpers are host arithmetic (-1: argument out of range). */
+#define SOPRO_PITCH_NT 64
+#define SOPRO_PITCH_P 256
+#define SOPRO_PITCH_TAIL 128
+#define SOPRO_PITCH_TILE 2048
+int64_t sopro_pitch_out_len(int64_t in_len, int64_t inc);
+int64_t sopro_pitch_chunk_out_cap(int64_t in_len);
+int64_t sopro_pitch_state_bytes(int32_t rows);
+int sopro_pitch_rows_f32(const float* in, int64_t in_stride, const int32_t* in_lens, int64_t in_cap, const int64_t* incs, const int32_t* bank_idx,
+                         const float* banks, int32_t n_banks, int32_t rows, void* state, int32_t flush, float* out, int64_t out_stride,
+                         int64_t out_cap, int32_t* out_lens, void* stream);
+
 /* ---- word timestamps: attention maps of the AR text cross-attention and the best monotonic path through them -------------- */
 /* No reference counterpart (the reference never materialises attention weights).  Definition: DESIGN.md "Word timestamps";
  * numpy / torch restatement: tests/align_ref.py.

@@ -7,6 +7,7 @@ monotonic path through them) is defined in DESIGN.md "Word timestamps" and inclu
     token_spans character range of every token id ``encode_text`` returns (BOS / EOS: empty)
     word_cues   tokens -> words -> sample ranges
     map_speed   a sample position before the speaking-rate stretch -> after it
+    map_pitch   a sample position before the pitch resampler -> after it
 """
 from __future__ import annotations
 
@@ -143,6 +144,21 @@ def map_speed(sample: int, step: int) -> int:
 
 def stretch_cues(cues: Sequence[WordCue], step: int) -> List[WordCue]:
     return [c._replace(start_sample=map_speed(c.start_sample, step), end_sample=map_speed(c.end_sample, step)) for c in cues]
+
+
+def map_pitch(sample: int, inc: int) -> int:
+    """A sample position before the pitch resampler -> after ``hip.pitch_shift`` at ``inc = hip.pitch_inc(semitones)``:
+    (sample << 32) // inc, the arithmetic of ``hip.pitch_out_len``.  The resampler's filter is symmetric about the read position
+    n * inc / 2^32 of output n (no delay), so the map is exact up to the floor: less than one sample."""
+    return (int(sample) << 32) // int(inc)
+
+
+def shift_cues(cues: Sequence[WordCue], inc: int) -> List[WordCue]:
+    """Cues of the waveform that went into the pitch resampler -> cues of what came out.  After ``stretch_cues(cues, step')`` (the
+    public ``pitch=``: stretch, then resample) a cue keeps the stretch's accuracy, +-240 samples of the stretched waveform, which the
+    resampler divides by rho = inc / 2^32 like every other distance: +-240 / rho samples (+-10 ms / rho; at most +-480 samples at -12
+    semitones), plus the floor's one sample."""
+    return [c._replace(start_sample=map_pitch(c.start_sample, inc), end_sample=map_pitch(c.end_sample, inc)) for c in cues]
 
 
 def long_cue(cue: WordCue, segment: int, off: int, edge_start: int, edge_end: int) -> LongWordCue:

@@ -12,7 +12,7 @@ import ctypes as C
 import gc
 import os
 import threading
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -271,6 +271,10 @@ SYMBOLS = {
     "sopro_tsm_chunk_out_cap": (_i64, [_i64]),
     "sopro_tsm_state_bytes": (_i64, [_i32]),
     "sopro_tsm_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i32, _p, _i32, _p, _p, _i64, _i64, _p, _p, _i32, _p]),
+    "sopro_pitch_out_len": (_i64, [_i64, _i64]),
+    "sopro_pitch_chunk_out_cap": (_i64, [_i64]),
+    "sopro_pitch_state_bytes": (_i64, [_i32]),
+    "sopro_pitch_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _p, _i32, _p, _i64, _i64, _p, _p]),
     "sopro_align_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "sopro_align_scores_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, C.c_uint32, _f32, _i32, _p, _i64,
                                          _i64, _p]),
@@ -1091,17 +1095,26 @@ def _tsm_check_rows(wav: torch.Tensor, lens_h: List[int], what: str) -> None:
         raise SoproHipError(f"{what}: the samples of a row must be contiguous")
 
 
-def time_stretch(wav: torch.Tensor, lens, speed, *, out: Optional[torch.Tensor] = None, deltas: bool = False):
+def _tsm_steps_given(steps, rows: int) -> List[int]:
+    """Steps handed over as they are (``prosody_steps``: a rate divided by a pitch ratio), one per row and in the operator's range."""
+    vals = [int(s) for s in steps]
+    if len(vals) != int(rows) or any(not (TSM_HS << 15) <= s <= (TSM_HS << 17) for s in vals):
+        raise ValueError(f"steps: one per row ({rows}) in [HS << 15, HS << 17], got {vals}")
+    return vals
+
+
+def time_stretch(wav: torch.Tensor, lens, speed, *, out: Optional[torch.Tensor] = None, deltas: bool = False, steps=None):
     """Speaking rate on the rows of a padded batch (sopro_tsm_rows_f32, one-shot form): ``wav`` fp32 [rows, >= max(lens)] on the
     device (rows ``wav.stride(0)`` apart, any pitch), ``lens`` valid samples per row, ``speed`` a float or one per row in [0.5, 2.0]
     (> 1: faster, shorter) -> (out [rows, max(out_lens)], out_lens) with row b valid for out_lens[b] = tsm_out_len(lens[b], step_b)
     samples.  One launch on the current stream and no synchronisation: the output lengths are host arithmetic.  ``out``: a
     [rows, >= max(out_lens)] fp32 buffer to write into (nothing past a row's out_len is touched).  ``deltas=True`` (tests,
-    debugging) also returns the chosen offsets d_k per row as lists, and checks the lengths the device reports (one host copy)."""
+    debugging) also returns the chosen offsets d_k per row as lists, and checks the lengths the device reports (one host copy).
+    ``steps``: one step per row instead of ``speed`` (which is then not looked at)."""
     lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
     rows = len(lens_h)
     _tsm_check_rows(wav, lens_h, "time_stretch")
-    steps_h = tsm_steps(speed, rows)
+    steps_h = tsm_steps(speed, rows) if steps is None else _tsm_steps_given(steps, rows)
     out_lens_h = [tsm_out_len(n, s) for n, s in zip(lens_h, steps_h)]
     cap = max(out_lens_h, default=0)
     if out is None:
@@ -1129,11 +1142,11 @@ class TimeStretchState:
     last position, samples received, a retained tail of < 1920 samples per row) lives on the device; every call is one launch and
     one small host copy (the lengths it produced)."""
 
-    def __init__(self, rows: int, speed, device):
+    def __init__(self, rows: int, speed, device, *, steps=None):
         self.rows = int(rows)
         if self.rows < 1:
             raise ValueError("rows >= 1")
-        self.steps = tsm_steps(speed, self.rows)
+        self.steps = tsm_steps(speed, self.rows) if steps is None else _tsm_steps_given(steps, self.rows)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise SoproHipError("TimeStretchState lives on a HIP device: the Sopro hot path has no CPU fallback")
@@ -1162,6 +1175,215 @@ class TimeStretchState:
     def flush(self, *, deltas: bool = False):
         """The remaining blocks (zero extension, the last one cut at the row's total output length); the state is fresh afterwards."""
         return self.feed(None, flush=True, deltas=deltas)
+
+
+# ---- pitch (sopro_pitch_*; definition in include/sopro_hip.h, numpy restatement in tests/pitch_ref.py) ----
+PITCH_NT, PITCH_P, PITCH_TILE = 64, 256, 2048
+PITCH_MIN, PITCH_MAX = -12.0, 12.0
+PITCH_ONE = 1 << 32  # the increment of pitch 0: the resampler is a copy there
+pitch_calls = 0  # calls of sopro_pitch_rows_f32 by this process (one launch each; a chunked call adds its small state update): the
+#                  pitch == 0 paths never add to it
+_pitch_banks: dict = {}  # (max(inc, 2^32), device) -> [257, 64] on the device; a tuple of such keys -> the stacked banks of a batch
+
+
+def pitch_inc(semitones) -> int:
+    """round(2^(semitones / 12) * 2^32): all the device sees of a pitch.  ``ValueError`` outside [-12, 12]."""
+    try:
+        v = float(semitones)
+    except (TypeError, ValueError):
+        raise ValueError(f"pitch must be a number of semitones in [{PITCH_MIN}, {PITCH_MAX}], got {semitones!r}") from None
+    if not (PITCH_MIN <= v <= PITCH_MAX):  # (NaN fails both comparisons)
+        raise ValueError(f"pitch must lie in [{PITCH_MIN}, {PITCH_MAX}] semitones, got {semitones!r}")
+    return min(1 << 33, max(1 << 31, int(round(2.0 ** (v / 12.0) * 4294967296.0))))
+
+
+def _per_row(value, rows: int, what: str) -> list:
+    if isinstance(value, (list, tuple)) or (hasattr(value, "__len__") and not isinstance(value, str)):
+        vals = list(value)
+        if len(vals) != int(rows):
+            raise ValueError(f"{what}: one value or one per row ({rows}), got {len(vals)}")
+        return vals
+    return [value] * int(rows)
+
+
+def pitch_incs(pitch, rows: int) -> List[int]:
+    """One increment per row from a number of semitones or one per row."""
+    return [pitch_inc(v) for v in _per_row(pitch, rows, "pitch")]
+
+
+def pitch_out_len(in_len: int, inc: int) -> int:
+    """Samples a row of ``in_len`` samples has after the resampler: (in_len << 32) // inc (sopro_pitch_out_len)."""
+    in_len, inc = int(in_len), int(inc)
+    if in_len < 0 or in_len > (1 << 30) or not (1 << 31) <= inc <= (1 << 33):
+        raise ValueError("in_len in [0, 2^30] and inc in [2^31, 2^33]")
+    return (in_len << 32) // inc
+
+
+def prosody_step(speed, pitch) -> Tuple[int, int]:
+    """(stretch step, resampler increment) for one speaking rate and one pitch: a shift by rho = inc / 2^32 is a stretch by rho and
+    a resample that reads rho times as fast, so the stretch runs at speed / rho: step' = round(speed * 480 * 65536 * 2^32 / inc)
+    (``tsm_step(speed)`` at pitch 0).  ``ValueError`` for a ``speed`` or a ``pitch`` out of range, and for a pair whose step' is
+    outside the stretch's own range."""
+    tsm_step(speed)
+    inc = pitch_inc(pitch)
+    step = int(round(float(speed) * TSM_HS * 65536 * 4294967296.0 / inc))
+    if not (TSM_HS << 15) <= step <= (TSM_HS << 17):
+        raise ValueError(f"speed={speed!r} with pitch={pitch!r}: speed / 2^(pitch / 12) must lie in [{SPEED_MIN}, {SPEED_MAX}] "
+                         "(the pitch shift stretches by 2^(pitch / 12) before it resamples)")
+    return step, inc
+
+
+def prosody_steps(speed, pitch, rows: int) -> List[Tuple[int, int]]:
+    """``prosody_step`` per row, from one value or one per row of each."""
+    return [prosody_step(sp, pt) for sp, pt in zip(_per_row(speed, rows, "speed"), _per_row(pitch, rows, "pitch"))]
+
+
+def is_plain(pairs) -> bool:
+    """Neither stage has anything to do for any row."""
+    return all(step == TSM_HS << 16 and inc == PITCH_ONE for step, inc in pairs)
+
+
+def pitch_bank_host(inc: int):
+    """The filter bank of an increment, float32 [257, 64] (numpy): Kaiser-windowed sinc rows (beta = 7, cut-off
+    0.5 min(1, 2^32 / inc) - 0.034 cycles per input sample), evaluated in float64, each row normalised to sum 1, rounded once."""
+    import numpy as np
+
+    fc = 0.5 * min(1.0, PITCH_ONE / max(int(inc), PITCH_ONE)) - 0.034
+    p = np.arange(PITCH_P + 1, dtype=np.float64)[:, None]
+    j = np.arange(PITCH_NT, dtype=np.float64)[None, :]
+    t = j - (PITCH_NT // 2 - 1) - p / PITCH_P
+    u = 1.0 - (t / (PITCH_NT // 2)) ** 2
+    w = np.where(u > 0.0, np.i0(7.0 * np.sqrt(np.maximum(u, 0.0))) / np.i0(7.0), 0.0)
+    g = 2.0 * fc * np.sinc(2.0 * fc * t) * w
+    return (g / g.sum(axis=1, keepdims=True)).astype(np.float32)
+
+
+def pitch_bank(inc: int, device) -> torch.Tensor:
+    """``pitch_bank_host`` on the device, cached per (max(inc, 2^32), device): every inc <= 2^32 has the same bank."""
+    key = (max(int(inc), PITCH_ONE), str(device))
+    t = _pitch_banks.get(key)
+    if t is None:
+        t = _pitch_banks[key] = torch.from_numpy(pitch_bank_host(key[0])).to(device)
+    return t
+
+
+def _pitch_banks_for(incs_h: List[int], device) -> Tuple[torch.Tensor, List[int]]:
+    """The banks a batch needs, [n_banks, 257, 64], and every row's index into them (rows at 2^32 never read theirs)."""
+    keys: List[int] = []
+    idx = []
+    for inc in incs_h:
+        k = max(int(inc), PITCH_ONE)
+        if k not in keys:
+            keys.append(k)
+        idx.append(keys.index(k))
+    if len(keys) == 1:
+        return pitch_bank(keys[0], device).unsqueeze(0), idx
+    key = (tuple(keys), str(device))
+    t = _pitch_banks.get(key)
+    if t is None:
+        if len(_pitch_banks) > 64:  # (a service with a new mix of pitches per batch: the stacks are cheap to make again)
+            for k in [k for k in _pitch_banks if isinstance(k[0], tuple)]:
+                del _pitch_banks[k]
+        t = _pitch_banks[key] = torch.stack([pitch_bank(k, device) for k in keys])
+    return t, idx
+
+
+def _pitch_launch(wav, in_cap: int, lens_h, incs_h, state, flush: bool, out):
+    """One sopro_pitch_rows_f32 on the current stream -> out_lens on the device."""
+    global pitch_calls
+    rows = len(lens_h)
+    dev = out.device
+    lib = load()
+    with torch.cuda.device(dev):
+        banks, idx = _pitch_banks_for(incs_h, dev)
+        args = torch.tensor([incs_h, lens_h, idx], dtype=torch.int64).to(dev)  # one upload
+        small = args[1:].to(torch.int32)
+        out_lens = torch.empty(rows, dtype=torch.int32, device=dev)
+        pitch_calls += 1
+        _check(lib.sopro_pitch_rows_f32(ptr(wav) if in_cap > 0 else None, int(wav.stride(0)) if in_cap > 0 else 0, small[0].data_ptr(), int(in_cap),
+                                        args[0].data_ptr(), small[1].data_ptr(), ptr(banks), int(banks.shape[0]), rows,
+                                        state.data_ptr() if state is not None else None, int(bool(flush)), ptr(out), int(out.stride(0)),
+                                        int(out.shape[1]), out_lens.data_ptr(), _stream()), "sopro_pitch_rows_f32")
+    return out_lens
+
+
+def pitch_shift(wav: torch.Tensor, lens, pitch, *, out: Optional[torch.Tensor] = None, incs=None):
+    """The resampler of the pitch control on the rows of a padded batch (sopro_pitch_rows_f32, one-shot form): ``wav`` fp32
+    [rows, >= max(lens)] on the device (rows ``wav.stride(0)`` apart, any alignment), ``lens`` valid samples per row, ``pitch``
+    semitones in [-12, 12], one value or one per row -> (out [rows, max(out_lens)], out_lens) with row b valid for out_lens[b] =
+    pitch_out_len(lens[b], inc_b) samples: every frequency of the row multiplied by 2^(pitch / 12), and the duration divided by it
+    (the public ``pitch=`` stretches by the same ratio first: ``prosody_steps``).  One launch on the current stream and no
+    synchronisation: the output lengths are host arithmetic.  ``out``: a [rows, >= max(out_lens)] fp32 buffer to write into
+    (nothing past a row's out_len is touched).  ``incs``: one increment per row instead of ``pitch``."""
+    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    rows = len(lens_h)
+    _tsm_check_rows(wav, lens_h, "pitch_shift")
+    incs_h = pitch_incs(pitch, rows) if incs is None else [int(v) for v in incs]
+    if len(incs_h) != rows:
+        raise ValueError(f"incs: one per row ({rows}), got {len(incs_h)}")
+    out_lens_h = [pitch_out_len(n, s) for n, s in zip(lens_h, incs_h)]
+    cap = max(out_lens_h, default=0)
+    if out is None:
+        out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=wav.device)
+    else:
+        ptr(out)
+        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
+            raise SoproHipError(f"pitch_shift: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+    if rows == 0:
+        return out[:, :0], []
+    _pitch_launch(wav, int(wav.shape[1]), lens_h, incs_h, None, True, out)
+    return out[:, :cap], out_lens_h
+
+
+def apply_prosody(wav: torch.Tensor, lens, pairs) -> Tuple[torch.Tensor, List[int]]:
+    """Speaking rate and pitch on a padded batch: ``time_stretch`` at every row's step', then ``pitch_shift`` at its inc
+    (``pairs`` from ``prosody_steps``), on the current stream.  A stage at its identity for every row is not launched; a row at
+    its identity in a launched stage comes back bit for bit."""
+    lens = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    steps, incs = [p[0] for p in pairs], [p[1] for p in pairs]
+    if any(s != TSM_HS << 16 for s in steps):
+        wav, lens = time_stretch(wav, lens, None, steps=steps)
+    if any(i != PITCH_ONE for i in incs):
+        wav, lens = pitch_shift(wav, lens, None, incs=incs)
+    return wav, lens
+
+
+class PitchShiftState:
+    """Chunked form of ``pitch_shift`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the outputs whose taps
+    are all in, ``flush`` the rest.  Any chunking followed by ``flush`` gives the one-shot result bit for bit.  The state (next
+    output, samples received, a retained tail of < 64 samples per row) lives on the device; every call is one launch plus the
+    state's small update and one small host copy (the lengths it produced)."""
+
+    def __init__(self, rows: int, pitch, device, *, incs=None):
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError("rows >= 1")
+        self.incs = pitch_incs(pitch, self.rows) if incs is None else [int(v) for v in incs]
+        if len(self.incs) != self.rows:
+            raise ValueError(f"incs: one per row ({self.rows}), got {len(self.incs)}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise SoproHipError("PitchShiftState lives on a HIP device: the Sopro hot path has no CPU fallback")
+        self.state = torch.zeros(int(load().sopro_pitch_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
+
+    def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False):
+        """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
+        if wav is None:
+            n, lens_h = 0, [0] * self.rows
+        else:
+            n = int(wav.shape[-1])
+            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            _tsm_check_rows(wav, lens_h, "PitchShiftState.feed")
+        cap = int(load().sopro_pitch_chunk_out_cap(n))
+        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        got = _pitch_launch(wav, n, lens_h, self.incs, self.state, flush, out).tolist()
+        if min(got) < 0:
+            raise SoproHipError("PitchShiftState: a row's outputs did not fit the output buffer")
+        return out[:, : max(got)], got
+
+    def flush(self):
+        """The remaining outputs (zero extension, up to the row's total output length); the state is fresh afterwards."""
+        return self.feed(None, flush=True)
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

@@ -182,12 +182,12 @@ class _Group(NamedTuple):
 
 
 def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top_p, temperature, anti_loop, style_strength, min_gen_frames,
-            seed, pauses_ms, join_kw, speed=1.0, word_cues=False, align_heads=None) -> Iterator[_Group]:
+            seed, pauses_ms, join_kw, speed=1.0, word_cues=False, align_heads=None, pitch=0.0) -> Iterator[_Group]:
     """Run the groups in order: one ``synthesize_batch`` and one ``hip.join_segments`` each, straight from the decoder's padded
     batch.  Segment k of the text draws with nonce (seed + k) & 0xFFFFFFFF and row id 0 - the sampler stream
     ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce.  ``speed``: the
     batch comes back stretched (rows in parallel, before the join: trimming, fades and cue times then refer to the audio as it is
-    heard) and the pauses shrink or grow with it."""
+    heard) and the pauses shrink or grow with it.  ``pitch``: the batch comes back shifted as well; the pauses follow ``speed`` only."""
     from . import hip
 
     n = len(segs)
@@ -200,7 +200,7 @@ def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top
         batch = tts.synthesize_batch([s.text for s in segs[k0: k0 + g]], [ref] * g, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                      anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed,
                                      nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, speed=speed, alignment=sink,
-                                     align_heads=align_heads)
+                                     align_heads=align_heads, pitch=pitch)
         piece, edges, offs = hip.join_segments(batch.wav, batch.lens, gaps[k0: k0 + g], **join_kw)
         yield _Group(k0, piece, edges, offs, batch, sink)
         k0 += g
@@ -219,18 +219,20 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
-                    keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None) -> LongformResult:
+                    keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None,
+                    pitch: float = 0.0) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
     (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k; at a ``speed`` other than 1.0 the
-    cue goes through ``align.map_speed`` first).  ``token_spans``: a callable text -> [(start, end)] per token id for tokenizers
+    cue goes through ``align.map_speed`` first, at a ``pitch`` other than 0.0 through ``align.stretch_cues`` at the stretch's own step
+    and ``align.shift_cues``).  ``token_spans``: a callable text -> [(start, end)] per token id for tokenizers
     that give no character offsets; ``align_heads``: the (layer, head) pairs to average."""
     import torch
 
     from . import align as A
     from . import hip
 
-    step = hip.tsm_step(speed)  # (a rate out of range is refused before anything runs)
+    step, inc = hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused before anything runs)
     if token_spans is not None and not callable(token_spans):
         raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
     spans_of = token_spans if token_spans is not None else (lambda t: A.token_spans(tts.tokenizer, t))
@@ -244,7 +246,8 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     words = [] if word_cues else None
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, word_cues=word_cues, align_heads=align_heads):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, word_cues=word_cues, align_heads=align_heads,
+                       pitch=pitch):
         pieces.append(grp.piece)
         offs, edges = grp.offs.tolist(), grp.edges.tolist()
         for i, (s, e) in enumerate(edges):
@@ -254,6 +257,8 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                 wc = A.word_cues(seg_text, spans_of(seg_text), grp.align[i].token_frames)
                 if step != hip.TSM_HS << 16:
                     wc = A.stretch_cues(wc, step)
+                if inc != hip.PITCH_ONE:
+                    wc = A.shift_cues(wc, inc)
                 words.extend(A.long_cue(c, grp.first + i, base + offs[i], s, e) for c in wc)
             if keep_parts:
                 n = grp.batch.lens[i]
@@ -268,15 +273,16 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True,
                 style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                 max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
-                fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0) -> Iterator[Any]:
+                fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0,
+                pitch: float = 0.0) -> Iterator[Any]:
     """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``)."""
     from . import hip
 
-    hip.tsm_step(speed)
+    hip.prosody_step(speed, pitch)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
         return
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, pitch=pitch):
         yield grp.piece.reshape(1, -1)

@@ -38,21 +38,29 @@ class SoproTTSStreamer:
                temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None,
                nar_context_frames: Optional[int] = None, min_gen_frames: Optional[int] = None,
-               text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0) -> Iterator[torch.Tensor]:
+               text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0,
+               pitch: float = 0.0) -> Iterator[torch.Tensor]:
         """``speed`` (new): speaking rate in [0.5, 2.0].  Other than 1.0, every decoded chunk is fed to a ``hip.TimeStretchState``
         and the blocks that became ready are yielded as [1, n * 480] (a step that completes no block yields nothing); a flush
         after the last chunk yields the rest.  The concatenation is ``hip.time_stretch`` of the unstretched stream's
-        concatenation, bit for bit."""
+        concatenation, bit for bit.  ``pitch`` (new): semitones in [-12, 12].  Other than 0.0, the chunks (stretched at
+        ``hip.prosody_step``'s step' where that is not the identity) are fed to a ``hip.PitchShiftState`` and the outputs whose
+        taps are in are yielded as [1, n]; both states are flushed after the last chunk.  The concatenation is
+        ``hip.apply_prosody`` of the plain stream's concatenation, bit for bit."""
         from . import hip
 
         tts = self.tts
-        tsm = hip.TimeStretchState(1, speed, tts.device) if hip.tsm_step(speed) != hip.TSM_HS << 16 else None
+        step, inc = hip.prosody_step(speed, pitch)
+        tsm = hip.TimeStretchState(1, None, tts.device, steps=[step]) if step != hip.TSM_HS << 16 else None
+        psh = hip.PitchShiftState(1, None, tts.device, incs=[inc]) if inc != hip.PITCH_ONE else None
 
         def rate(wav: Optional[torch.Tensor], last: bool = False) -> Optional[torch.Tensor]:
-            if tsm is None or (wav is None and not last):
-                return wav
-            out, n = tsm.feed(wav, flush=last)
-            return out[:, : n[0]] if n[0] > 0 else None
+            for st in (tsm, psh):  # (the stretch's flush feeds the resampler before that is flushed)
+                if st is None or (wav is None and not last):
+                    continue
+                out, n = st.feed(wav, flush=last)
+                wav = out[:, : n[0]] if n[0] > 0 else None
+            return wav
 
         model = tts.model
         ids = text_ids if text_ids is not None else tts.encode_text(text)
@@ -96,7 +104,7 @@ class SoproTTSStreamer:
             wav = rate(refine_and_emit(len(hist)))
             if wav is not None:
                 yield wav
-        if tsm is not None:
+        if tsm is not None or psh is not None:
             wav = rate(None, last=True)
             if wav is not None:
                 yield wav
@@ -105,14 +113,15 @@ class SoproTTSStreamer:
 @torch.inference_mode()
 def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
            ref: Optional[PreparedReference] = None, chunk_frames: int = 6, cache_trim: str = "none", speed: float = 1.0,
-           **kwargs) -> Iterator[torch.Tensor]:
-    """reference: src/sopro/streaming.py:133-152 (``cache_trim`` and ``speed`` are new: see MimiStreamDecoder, SoproTTSStreamer.stream)"""
+           pitch: float = 0.0, **kwargs) -> Iterator[torch.Tensor]:
+    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed`` and ``pitch`` are new: see MimiStreamDecoder,
+    SoproTTSStreamer.stream)"""
     from . import hip
 
-    hip.tsm_step(speed)  # (a rate out of range is refused here, not at the first chunk)
+    hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused here, not at the first chunk)
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
-                           chunk_frames=chunk_frames, speed=speed, **kwargs)
+                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, **kwargs)
 
 
 def refuse_speed(speed, what: str) -> None:
@@ -121,6 +130,15 @@ def refuse_speed(speed, what: str) -> None:
 
     if hip.tsm_step(speed) != hip.TSM_HS << 16:
         raise NotImplementedError(f"{what} has no speaking-rate control (speed={speed!r}): use stream(), synthesize_batch() or "
+                                  "SynthesisService.submit() in mode='batch'")
+
+
+def refuse_pitch(pitch, what: str) -> None:
+    """The lockstep / frame-level paths have no pitch control either: anything but 0.0 is an error, never ignored."""
+    from . import hip
+
+    if hip.pitch_inc(pitch) != hip.PITCH_ONE:
+        raise NotImplementedError(f"{what} has no pitch control (pitch={pitch!r}): use stream(), synthesize_batch() or "
                                   "SynthesisService.submit() in mode='batch'")
 
 
@@ -175,14 +193,16 @@ def stream_batch(tts, texts: Sequence[str], refs: Sequence, *, chunk_frames: int
                  min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
                  nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                  phase_locks: Optional[tuple] = None, timings: Optional[Dict[str, float]] = None,
-                 alive: Optional[Callable[[int], bool]] = None, speed: float = 1.0) -> Iterator[List[Optional[torch.Tensor]]]:
+                 alive: Optional[Callable[[int], bool]] = None, speed: float = 1.0,
+                 pitch: float = 0.0) -> Iterator[List[Optional[torch.Tensor]]]:
     """B utterances streamed in lockstep.  Yields, per step, a list of B entries: a [1, n * 1920] chunk or None.  Row b's non-None
     chunks are what ``stream(texts[b], ref=refs[b], seed=seeds[b], ...)`` yields: same chunk sizes, same stop rule (first EOS).
     ``seeds``: one per row (None: a fresh take for that row).  ``phase_locks`` = (AR lock, bulk lock): held around the AR advance and
     around refinement + decode of every step (a serving lane shares its device with whole-utterance batches).  ``timings``: seconds
     of host wall time accumulated under "ar", "refine", "decode".  ``alive(b)`` (a server): False once row b's consumer has gone - the
-    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0 (batched streams have no rate control)."""
+    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0 (batched streams have neither control)."""
     refuse_speed(speed, "stream_batch")
+    refuse_pitch(pitch, "stream_batch")
     model = tts.model
     B = len(texts)
     if B == 0 or len(refs) != B:

@@ -128,14 +128,18 @@ class SoproTTS:
                    ref_tokens_tq: Optional[torch.Tensor] = None, max_frames: int = 400, top_p: float = 0.9,
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
-                   seed: Optional[int] = None, speed: float = 1.0) -> torch.Tensor:
+                   seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
         draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed`` (new): speaking rate
-        in [0.5, 2.0], applied to the decoded waveform by ``hip.time_stretch`` (pitch-preserving; 1.0 launches nothing)."""
+        in [0.5, 2.0], applied to the decoded waveform by ``hip.time_stretch`` (pitch-preserving; 1.0 launches nothing).
+        ``pitch`` (new): semitones in [-12, 12], applied to the decoded waveform as a stretch by rho = 2^(pitch / 12) and a
+        band-limited resample that reads rho times as fast (``hip.prosody_step``, ``hip.pitch_shift``): the duration stays what
+        ``speed`` makes it and every frequency - formants included - is multiplied by rho; 0.0 launches nothing.  ``speed / rho``
+        must lie in [0.5, 2.0]."""
         from . import hip
 
-        step = hip.tsm_step(speed)
+        step, inc = hip.prosody_step(speed, pitch)
         text_ids = self.encode_text(text)
         if ref is None:
             ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
@@ -144,9 +148,9 @@ class SoproTTS:
             style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
             min_gen_frames=min_gen_frames, seed=seed)
         wav = self.codec.decode_full(tokens)
-        if step == hip.TSM_HS << 16 or wav.numel() == 0:
+        if hip.is_plain([(step, inc)]) or wav.numel() == 0:
             return wav
-        out, _ = hip.time_stretch(wav.reshape(1, -1), [int(wav.shape[-1])], speed)
+        out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
         return out.reshape(1, 1, -1)
 
     @torch.inference_mode()
@@ -157,7 +161,7 @@ class SoproTTS:
                          phase_locks: Optional[tuple] = None, seed: Optional[int] = None, nonces: Optional[Sequence[int]] = None,
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
                          speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
-                         align_heads=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         align_heads=None, pitch: Union[float, Sequence[float]] = 0.0) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
@@ -166,6 +170,9 @@ class SoproTTS:
         ``speed``: speaking rate in [0.5, 2.0], one float or one per row; the decoder's padded batch is stretched in one launch
         on the bulk stream before it is sliced (``hip.time_stretch``), so ``PaddedBatch.wav`` / ``lens`` are the stretched rows
         and ``tokens`` stay what the model produced.  All rows at 1.0: nothing is launched.
+        ``pitch``: semitones in [-12, 12], one float or one per row (see ``synthesize``); the stretched batch is resampled in one
+        more launch (``hip.pitch_shift``) before it is sliced.  All rows at 0.0: nothing is launched, and a row at 0.0 among
+        shifted ones comes back bit for bit.
         ``alignment``: a sink like ``timings`` - a list passed in is filled with one ``align.Alignment`` per row (frame -> text
         position path, frame range per position, confidence; in frames, before any stretch) by a post-pass on the bulk stream
         (``model.align_batch``: the AR stack replayed over the generated tokens, ``hip.align_scores`` / ``hip.align_paths``);
@@ -176,8 +183,8 @@ class SoproTTS:
         from . import hip
 
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
-        steps = hip.tsm_steps(speed, len(ids))
-        stretch = any(s != hip.TSM_HS << 16 for s in steps)
+        prosody = hip.prosody_steps(speed, pitch, len(ids))
+        stretch = not hip.is_plain(prosody)  # (a rate, a pitch or both)
         if alignment is not None:
             self.model._align_heads(align_heads)  # (a bad selection is refused before anything runs)
         locks = tuple(phase_locks) if phase_locks is not None else ()
@@ -256,8 +263,8 @@ class SoproTTS:
                 alignment[:] = self.model.align_batch(state["prep"], state, heads=align_heads)
             hop = int(self.codec.mc.frame_samples)
             n_samples = [n * hop for n in lens]
-            if stretch:  # (rows at 1.0 in a mixed batch come back bit for bit: the operator is the identity there)
-                wav, n_samples = hip.time_stretch(wav, n_samples, speed)
+            if stretch:  # (rows at 1.0 / 0.0 in a mixed batch come back bit for bit: both operators are the identity there)
+                wav, n_samples = hip.apply_prosody(wav, n_samples, prosody)
             toks = None
             if padded:  # (the engine's own token matrix: copied before the next pass overwrites it, complete before any stream reads it)
                 toks = codes.long()
@@ -272,18 +279,20 @@ class SoproTTS:
                          ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
                          top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                          ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
-                         speed: float = 1.0):
+                         speed: float = 1.0, pitch: float = 0.0):
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
         ``align.Alignment`` with its ``confidence``.  Cues are whole frames (1920 samples); with ``speed`` other than 1.0 they are
-        mapped by ``align.map_speed`` (accurate to +-240 samples, the stretch's search radius).  ``token_spans``: the character span
+        mapped by ``align.map_speed`` (accurate to +-240 samples, the stretch's search radius), with ``pitch`` other than 0.0 by
+        ``align.stretch_cues`` at the stretch's own step and then ``align.shift_cues`` (+-240 / 2^(pitch / 12) samples: see there).
+        ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
         ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12)."""
         from . import align as A
         from . import hip
 
-        step = hip.tsm_step(speed)
+        step, inc = hip.prosody_step(speed, pitch)
         text_ids = self.encode_text(text)
         spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
         if len(spans) != int(text_ids.numel()):
@@ -297,43 +306,50 @@ class SoproTTS:
             min_gen_frames=min_gen_frames, seed=seed, alignment=sink, align_heads=align_heads)[0]
         wav = self.codec.decode_full(tokens)
         words = A.word_cues(text, spans, sink[0].token_frames, hop=int(self.codec.mc.frame_samples))
-        if step != hip.TSM_HS << 16 and wav.numel() > 0:
-            out, _ = hip.time_stretch(wav.reshape(1, -1), [int(wav.shape[-1])], speed)
+        if not hip.is_plain([(step, inc)]) and wav.numel() > 0:
+            out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
             wav = out.reshape(1, 1, -1)
-            words = A.stretch_cues(words, step)
+            if step != hip.TSM_HS << 16:
+                words = A.stretch_cues(words, step)
+            if inc != hip.PITCH_ONE:
+                words = A.shift_cues(words, inc)
         return A.TimedResult(wav, words, sink[0])
 
     def clone_lane(self) -> "SoproTTS":
         """Another engine over the same device weights (own streams / scratch), for pipelining batches."""
         return SoproTTS(self.model.clone_lane(), self.cfg, self.tokenizer, self.codec.clone_lane(), str(self.device))
 
-    def stream(self, text: str, *, speed: float = 1.0, **kwargs) -> Iterator[torch.Tensor]:
+    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, **kwargs) -> Iterator[torch.Tensor]:
         """reference: src/sopro/model.py:577-580.  ``speed`` (new): speaking rate in [0.5, 2.0]; every decoded chunk goes through
-        the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream)."""
+        the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream).
+        ``pitch`` (new): semitones in [-12, 12]; the chunks then also go through the chunked resampler and come out as [1, n]."""
         from .align import refuse_timing
         from .streaming import stream
 
         refuse_timing(kwargs, "stream")
-        return stream(self, text, speed=speed, **kwargs)
+        return stream(self, text, speed=speed, pitch=pitch, **kwargs)
 
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
                      nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
-                     speed: float = 1.0, **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
+                     speed: float = 1.0, pitch: float = 0.0, **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
         entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
-        A speaking rate is not available here (``speed`` other than 1.0 raises): use ``stream`` or ``synthesize_batch``."""
+        A speaking rate or a pitch is not available here (``speed`` other than 1.0 or ``pitch`` other than 0.0 raises): use
+        ``stream`` or ``synthesize_batch``."""
         from .align import refuse_timing
-        from .streaming import refuse_speed, stream_batch
+        from .streaming import refuse_pitch, refuse_speed, stream_batch
 
         refuse_timing(kwargs, "stream_batch")
         refuse_speed(speed, "stream_batch")
+        refuse_pitch(pitch, "stream_batch")
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
-                            cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, **kwargs)
+                            cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, pitch=pitch,
+                            **kwargs)
 
-    def synthesize_long(self, text: str, *, speed: float = 1.0, **kwargs):
+    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, **kwargs):
         """New: a text of any length (a paragraph, an article, a chapter) -> ``LongformResult``: ``wav`` [1, 1, N] on the device and
         ``segments`` [(text, start sample, end sample)] in it.  The text is cut into sentences (``longform.split_text``,
         ``max_chars``), the voice is prepared once, groups of up to ``max_rows`` segments (``plan``: "throughput", "latency" or a
@@ -344,21 +360,24 @@ class SoproTTS:
         ``synthesize(segment_k, ref=ref, seed=seed + k)`` does.  ``keep_parts=True`` also returns every segment's untrimmed
         waveform and tokens (``parts``) and the kept range (``edges``).  ``speed``: speaking rate in [0.5, 2.0]; every group's
         padded batch is stretched before the join (``parts`` are the stretched rows, cue times refer to the stretched audio) and
-        the pauses are divided by it.  ``word_cues=True`` also fills ``words`` (one ``align.LongWordCue`` per word, samples in the
+        the pauses are divided by it.  ``pitch``: semitones in [-12, 12]; every group's batch is stretched and resampled before the
+        join (see ``synthesize``), the pauses are not touched by it.  ``word_cues=True`` also fills ``words`` (one ``align.LongWordCue`` per word, samples in the
         joined waveform).  Full parameter list: ``longform.synthesize_long``."""
         from .longform import synthesize_long
 
-        return synthesize_long(self, text, speed=speed, **kwargs)
+        return synthesize_long(self, text, speed=speed, pitch=pitch, **kwargs)
 
-    def stream_long(self, text: str, *, speed: float = 1.0, **kwargs) -> Iterator[torch.Tensor]:
+    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, **kwargs) -> Iterator[torch.Tensor]:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
-        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed``)."""
+        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed`` and ``pitch``)."""
+        from . import hip
         from .align import refuse_timing
         from .longform import stream_long
 
         refuse_timing(kwargs, "stream_long")
-        return stream_long(self, text, speed=speed, **kwargs)
+        hip.prosody_step(speed, pitch)  # (refused here, not at the first piece)
+        return stream_long(self, text, speed=speed, pitch=pitch, **kwargs)
 
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""

@@ -936,6 +936,71 @@ int sopro_pitch_rows_f32(const float* in, int64_t in_stride, const int32_t* in_l
                          const float* banks, int32_t n_banks, int32_t rows, void* state, int32_t flush, float* out, int64_t out_stride,
                          int64_t out_cap, int32_t* out_lens, void* stream);
 
+/* ---- watermark: a keyed spread-spectrum mark in the rows of a padded batch, and its detector ------------------------------ */
+/* Nothing the engine emits can otherwise be told from a recording, so a deployment may add a keyed, tagged mark to every waveform
+ * as the last step, and ask later whether a clip carries it.  No reference counterpart.  24 kHz mono fp32.  Every fp32 operation
+ * of the embedder is rounded on its own (no contraction) and the library evaluates no transcendental function (the host makes the
+ * tables): the embedder has one right answer, bit for bit (tests/wm_ref.py restates both halves in numpy).
+ *   HS = 480: the envelope grid; tab[HS] is the stretch's raised-cosine table.  P = 8192: the carrier period in samples.  CH = 2
+ *   samples per chip, NC = P / CH = 4096 chips.  SHIFT = 32 samples per tag step; tags lie in [0, 256) and 256 * SHIFT == P.
+ * Carrier (host).  fmix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16, all mod 2^32.  For a key
+ *   (uint64, words lo / hi), lane l in {0, 1} and chip i < NC: h = fmix(fmix((i * 0x9E3779B1 + lo) mod 2^32) ^ hi ^ ((l * 0x7F4A7C15)
+ *   mod 2^32)); s_l(i) = +1 if bit 31 of h is clear, else -1; c_l[n] = s_l(n / CH), n < P.  The table of a (key, tag) is int8 [P]:
+ *   car[n] = c_0[n] + c_1[(n - SHIFT * tag) mod P], values in {-2, 0, 2}.  Lane 0 is the sync carrier, lane 1 the same kind of
+ *   sequence rotated by the tag.
+ * Envelope of a row x[0 .. L), zero-extended: for k = 0 .. ceil(L / HS) + 1, e_k = max |x[n]| over (k - 1) HS <= n < (k + 1) HS,
+ *   0 <= n < L (an empty range gives 0; a maximum is exact in any order).  For sample n with k = n / HS, r = n mod HS:
+ *   g(n) = fl32(e_k + fl32(tab[r] * fl32(e_{k+1} - e_k))).
+ * Embed: y[n] = fl32(x[n] + fl32(fl32(alpha * g(n)) * cf)), cf = 0.5f * car[n mod P] (exact), alpha = fl32(10^(strength_db / 20))
+ *   made by the host (strength_db in [-48, -18]).  A row whose carrier index is negative is a copy, bit for bit, and no table is
+ *   read.  Silence stays silent; the length does not change.
+ * Chunked form (same numbers): `state` holds, per row, (samples emitted, samples received, the retained input tail).  A call
+ *   appends in[row, 0 .. in_lens[row]) to the row and computes every block k (samples [k HS, (k + 1) HS)) with received >= (k + 2) HS:
+ *   both of its envelope points are then final.  With `flush` the rest is computed with zero extension up to the samples received and
+ *   the row's state is zeroed (a fresh row).  Any chunking followed by a flush gives the one-shot result bit for bit.  The retained
+ *   tail is everything from (k_next - 1) HS on; block k_next was not ready, so received < (k_next + 2) HS and the tail holds fewer
+ *   than 3 HS = 1440 samples <= SOPRO_WM_TAIL.  Rows without a carrier follow the same schedule.
+ * Output of a call: out[row, 0 .. out_lens[row]) = the samples of the blocks computed by THIS call, in order (one-shot: the whole
+ *   y).  Nothing at or past out_cap or past out_lens[row] is written; a row whose samples do not fit gets out_lens[row] = -1, nothing
+ *   written and a zeroed state (a sizing error of the caller: a one-shot call needs out_cap >= in_lens[row],
+ *   sopro_wm_chunk_out_cap(in_cap) = in_cap + SOPRO_WM_TAIL bounds one chunked call, flush included).
+ *   in_lens int32 [rows] (clamped to [0, in_cap]), car_idx int32 [rows] (negative: no mark; clamped to n_cars - 1) into cars int8
+ *   [n_cars][P] (4-byte aligned), alphas float [rows], tab float [HS], out_lens int32 [rows]: device memory.  state: NULL for a
+ *   one-shot call (flush must be set), else sopro_wm_state_bytes(rows) bytes of device memory, zeroed before a row's first chunk.
+ *   Rows need no alignment beyond 4 bytes.  sopro_wm_embed_rows_f32 enqueues one launch over (tile of SOPRO_WM_TILE samples, row) -
+ *   with a state a second, small one that updates it after every tile has read the tail - on `stream`, allocates nothing and
+ *   synchronises nothing.  A tile recomputes the envelope points it needs from x[tile - HS .. tile + SOPRO_WM_TILE + HS).
+ * Detect, for a row y[0 .. L) and a key (sums in steps 2 to 4 have no prescribed order on the device):
+ *   1. w[0] = y[0], w[n] = fl32(y[n] - y[n-1]); g(n) the envelope above, taken of y; pk = max |y|; u[n] = w[n] / g(n) where
+ *      g(n) > fl32(1e-3f * pk), else 0.
+ *   2. f[r] = sum over m of u[r + m P], r < P                                            (sopro_wm_fold_rows_f32: m ascending, fp32)
+ *   3. templates d_l[n] = c_l[n] - c_l[(n - 1) mod P] (int8, values in {-2, 0, 2}, from the host);
+ *      R_l[o] = sum_n f[(n + o) mod P] * d_l[n] for every o < P and both lanes             (sopro_wm_corr_rows_f32: n ascending, fp32)
+ *   4. per lane o_l = argmax R_l (lowest index on a tie), z_l = (R_l[o_l] - mean(R_l)) / std(R_l) over all P offsets (population
+ *      std; 0 when it is 0)                    (sopro_wm_peak_rows_f32: fp32 partial sums of 32 terms, combined in float64)
+ *   5. (host) offset = o_0 (a clip cropped by c samples gives -c mod P); tag = (((o_1 - o_0) mod P + SHIFT / 2) / SHIFT) mod 256;
+ *      score = min(z_0, z_1); present = score >= 6.  L == 0 or pk == 0: score 0, not present.
+ *   fold: workspace = sopro_wm_fold_ws_bytes(rows, in_cap) bytes of device memory (the block maxima of every row); f float
+ *   [rows][P].  Two launches (block maxima; peak and fold).  corr: f float [rows][P], dtab int8 [n_keys][2][P] (4-byte aligned),
+ *   key_idx int32 [rows] (clamped to [0, n_keys)), R float [rows][2][P]; one launch over (tile of 1024 offsets, row), f and both
+ *   templates of the row in LDS.  peak: out int32 [rows][4] = (o_0, o_1, bits of z_0, bits of z_1); one launch, one workgroup per
+ *   (lane, row).  All of them enqueue on `stream`, allocate nothing and synchronise nothing. */
+#define SOPRO_WM_HS 480
+#define SOPRO_WM_P 8192
+#define SOPRO_WM_SHIFT 32
+#define SOPRO_WM_TAIL 1536
+#define SOPRO_WM_TILE 3840
+int64_t sopro_wm_state_bytes(int32_t rows);
+int64_t sopro_wm_chunk_out_cap(int64_t in_len);
+int64_t sopro_wm_fold_ws_bytes(int32_t rows, int64_t in_cap);
+int sopro_wm_embed_rows_f32(const float* in, int64_t in_stride, const int32_t* in_lens, int64_t in_cap, const int32_t* car_idx, const int8_t* cars,
+                            int32_t n_cars, const float* alphas, int32_t rows, void* state, int32_t flush, const float* tab, float* out,
+                            int64_t out_stride, int64_t out_cap, int32_t* out_lens, void* stream);
+int sopro_wm_fold_rows_f32(const float* in, int64_t in_stride, const int32_t* in_lens, int64_t in_cap, int32_t rows, const float* tab, void* workspace,
+                           float* f, void* stream);
+int sopro_wm_corr_rows_f32(const float* f, const int8_t* dtab, int32_t n_keys, const int32_t* key_idx, int32_t rows, float* R, void* stream);
+int sopro_wm_peak_rows_f32(const float* R, int32_t rows, int32_t* out, void* stream);
+
 /* ---- word timestamps: attention maps of the AR text cross-attention and the best monotonic path through them -------------- */
 /* No reference counterpart (the reference never materialises attention weights).  Definition: DESIGN.md "Word timestamps";
  * numpy / torch restatement: tests/align_ref.py.

@@ -1,8 +1,10 @@
 """sopro_amd: MI355X-native engine for the Sopro TTS synthesize/stream hot path.
 
-``SoproTTS`` is the only public name, as in the reference package (src/sopro/__init__.py:3-5).
+``SoproTTS`` is the public name of the reference package (src/sopro/__init__.py:3-5); ``Watermark`` is what its ``watermark=``
+keyword takes (``sopro_amd.watermark``).
 Importing the package does not need a GPU; constructing an engine does (and raises otherwise).
 """
 from .tts import SoproTTS  # noqa: F401
+from .watermark import Watermark  # noqa: F401
 
-__all__ = ["SoproTTS"]
+__all__ = ["SoproTTS", "Watermark"]

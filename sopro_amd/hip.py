@@ -275,6 +275,13 @@ SYMBOLS = {
     "sopro_pitch_chunk_out_cap": (_i64, [_i64]),
     "sopro_pitch_state_bytes": (_i64, [_i32]),
     "sopro_pitch_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _i32, _p, _i32, _p, _i64, _i64, _p, _p]),
+    "sopro_wm_state_bytes": (_i64, [_i32]),
+    "sopro_wm_chunk_out_cap": (_i64, [_i64]),
+    "sopro_wm_fold_ws_bytes": (_i64, [_i32, _i64]),
+    "sopro_wm_embed_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _p, _i32, _p, _i32, _p, _p, _i64, _i64, _p, _p]),
+    "sopro_wm_fold_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _p, _p]),
+    "sopro_wm_corr_rows_f32": (C.c_int, [_p, _p, _i32, _p, _i32, _p, _p]),
+    "sopro_wm_peak_rows_f32": (C.c_int, [_p, _i32, _p, _p]),
     "sopro_align_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "sopro_align_scores_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, C.c_uint32, _f32, _i32, _p, _i64,
                                          _i64, _p]),
@@ -1384,6 +1391,147 @@ class PitchShiftState:
     def flush(self):
         """The remaining outputs (zero extension, up to the row's total output length); the state is fresh afterwards."""
         return self.feed(None, flush=True)
+
+
+# ---- watermark (sopro_wm_*; definition in include/sopro_hip.h, numpy restatement in tests/wm_ref.py; host tables in watermark.py) ----
+WM_HS, WM_P, WM_TILE, WM_TAIL = 480, 8192, 3840, 1536
+_wm_calls = {"embed": 0, "detect": 0}  # calls of sopro_wm_embed_rows_f32 / of the detector's launch sequence by this process
+
+
+def wm_calls() -> int:
+    """Calls of the watermark kernels by this process (embedder and detector together): the ``watermark=None`` paths never add to it."""
+    return _wm_calls["embed"] + _wm_calls["detect"]
+
+
+def _wm_launch(wav, in_cap: int, lens_h, marks, state, flush: bool, out):
+    """One sopro_wm_embed_rows_f32 on the current stream -> out_lens on the device."""
+    import numpy as np
+
+    from . import watermark as wm
+
+    rows = len(lens_h)
+    dev = out.device
+    lib = load()
+    with torch.cuda.device(dev):
+        cars, idx = wm.carrier_tables(marks, dev)
+        alpha_bits = np.array([m.alpha if m is not None else 0.0 for m in marks], dtype=np.float32).view(np.int32).tolist()
+        args = torch.tensor([lens_h, idx, alpha_bits], dtype=torch.int32).to(dev)  # one upload
+        out_lens = torch.empty(rows, dtype=torch.int32, device=dev)
+        _wm_calls["embed"] += 1
+        _check(lib.sopro_wm_embed_rows_f32(ptr(wav) if in_cap > 0 else None, int(wav.stride(0)) if in_cap > 0 else 0, args[0].data_ptr(), int(in_cap),
+                                           args[1].data_ptr(), cars.data_ptr(), int(cars.shape[0]), args[2].data_ptr(), rows,
+                                           state.data_ptr() if state is not None else None, int(bool(flush)), ptr(fade_table(WM_HS, dev)),
+                                           ptr(out), int(out.stride(0)), int(out.shape[1]), out_lens.data_ptr(), _stream()),
+               "sopro_wm_embed_rows_f32")
+    return out_lens
+
+
+def wm_embed(wav: torch.Tensor, lens, marks, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The watermark on the rows of a padded batch (sopro_wm_embed_rows_f32, one-shot form): ``wav`` fp32 [rows, >= max(lens)] on
+    the device (rows ``wav.stride(0)`` apart, any alignment), ``lens`` valid samples per row, ``marks`` one ``Watermark`` or None,
+    or one per row -> out [rows, max(lens)], row b valid for lens[b] samples: the row plus its mark's carrier at ``strength_db``
+    below the row's local peak; a row whose mark is None comes back bit for bit.  One launch on the current stream and no
+    synchronisation.  ``out``: a [rows, >= max(lens)] fp32 buffer to write into (nothing past a row's length is touched); it must
+    not overlap ``wav`` (a tile reads its neighbours' samples).  All marks None: nothing is launched and ``wav[:, :max(lens)]`` is
+    returned as it is."""
+    from . import watermark as wm
+
+    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    rows = len(lens_h)
+    _tsm_check_rows(wav, lens_h, "wm_embed")
+    marks = wm.per_row(marks, rows, "marks")
+    cap = max(lens_h, default=0)
+    if out is not None:
+        ptr(out)
+        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
+            raise SoproHipError(f"wm_embed: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+    if rows == 0 or all(m is None for m in marks):
+        if out is None:
+            return wav[:, :cap]
+        out[:, :cap].copy_(wav[:, :cap])  # (a caller that asked for its own buffer gets the rows there)
+        return out[:, :cap]
+    if out is None:
+        out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=wav.device)
+    _wm_launch(wav, int(wav.shape[1]), lens_h, marks, None, True, out)
+    return out[:, :cap]
+
+
+class WatermarkState:
+    """Chunked form of ``wm_embed`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the 480-sample blocks whose
+    envelope is final (a chunk comes out up to 1440 samples short, and the rest follows), ``flush`` the rest.  Any chunking followed
+    by ``flush`` gives the one-shot result bit for bit.  The state (samples emitted, samples received, a retained tail of < 1440
+    samples per row) lives on the device; every call is one launch plus the state's small update and one small host copy (the
+    lengths it produced)."""
+
+    def __init__(self, rows: int, marks, device):
+        from . import watermark as wm
+
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError("rows >= 1")
+        self.marks = wm.per_row(marks, self.rows, "marks")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise SoproHipError("WatermarkState lives on a HIP device: the Sopro hot path has no CPU fallback")
+        self.state = torch.zeros(int(load().sopro_wm_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
+
+    def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False):
+        """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
+        if wav is None:
+            n, lens_h = 0, [0] * self.rows
+        else:
+            n = int(wav.shape[-1])
+            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            _tsm_check_rows(wav, lens_h, "WatermarkState.feed")
+        cap = int(load().sopro_wm_chunk_out_cap(n))
+        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        got = _wm_launch(wav, n, lens_h, self.marks, self.state, flush, out).tolist()
+        if min(got) < 0:
+            raise SoproHipError("WatermarkState: a row's samples did not fit the output buffer")
+        return out[:, : max(got)], got
+
+    def flush(self):
+        """The remaining samples (zero extension of the envelope); the state is fresh afterwards."""
+        return self.feed(None, flush=True)
+
+
+def wm_detect_rows(wav: torch.Tensor, lens, keys, *, details: bool = False):
+    """The watermark detector on the rows of a padded batch (sopro_wm_fold_rows_f32, _corr_rows_f32, _peak_rows_f32): ``wav`` fp32
+    [rows, >= max(lens)] on the device, ``lens`` valid samples per row, ``keys`` one 64-bit key per row -> one
+    ``watermark.WatermarkResult`` per row.  Four launches on the current stream and one small host copy (two offsets and two peak
+    statistics per row).  ``details=True`` (tests) also returns the folded rows f [rows, 8192] and the correlations R [rows, 2, 8192]."""
+    from . import watermark as wm
+
+    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    rows = len(lens_h)
+    _tsm_check_rows(wav, lens_h, "wm_detect_rows")
+    keys = list(keys)
+    if len(keys) != rows:
+        raise ValueError(f"keys: one per row ({rows}), got {len(keys)}")
+    if rows == 0:
+        return ([], None, None) if details else []
+    dev = wav.device
+    lib = load()
+    in_cap = int(wav.shape[1])
+    with torch.cuda.device(dev):
+        dtab, idx = wm.template_tables(keys, dev)
+        args = torch.tensor([lens_h, idx], dtype=torch.int32).to(dev)  # one upload
+        ws = torch.empty(max(1, int(lib.sopro_wm_fold_ws_bytes(rows, in_cap)) // 4), dtype=torch.float32, device=dev)
+        f = torch.empty(rows, WM_P, dtype=torch.float32, device=dev)
+        R = torch.empty(rows, 2, WM_P, dtype=torch.float32, device=dev)
+        pk = torch.empty(rows, 4, dtype=torch.int32, device=dev)
+        s = _stream()
+        _wm_calls["detect"] += 1
+        _check(lib.sopro_wm_fold_rows_f32(ptr(wav), int(wav.stride(0)), args[0].data_ptr(), in_cap, rows, ptr(fade_table(WM_HS, dev)), ws.data_ptr(),
+                                          f.data_ptr(), s), "sopro_wm_fold_rows_f32")
+        _check(lib.sopro_wm_corr_rows_f32(f.data_ptr(), dtab.data_ptr(), int(dtab.shape[0]), args[1].data_ptr(), rows, R.data_ptr(), s),
+               "sopro_wm_corr_rows_f32")
+        _check(lib.sopro_wm_peak_rows_f32(R.data_ptr(), rows, pk.data_ptr(), s), "sopro_wm_peak_rows_f32")
+        host = pk.cpu()
+    o = host[:, :2].tolist()
+    z = host[:, 2:].contiguous().view(torch.float32).tolist()
+    res = [wm.result_of(o[b][0], o[b][1], z[b][0], z[b][1]) for b in range(rows)]
+    return (res, f, R) if details else res
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

@@ -220,19 +220,23 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
                     keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None,
-                    pitch: float = 0.0) -> LongformResult:
+                    pitch: float = 0.0, watermark=None) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
     (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k; at a ``speed`` other than 1.0 the
     cue goes through ``align.map_speed`` first, at a ``pitch`` other than 0.0 through ``align.stretch_cues`` at the stretch's own step
     and ``align.shift_cues``).  ``token_spans``: a callable text -> [(start, end)] per token id for tokenizers
-    that give no character offsets; ``align_heads``: the (layer, head) pairs to average."""
+    that give no character offsets; ``align_heads``: the (layer, head) pairs to average.  ``watermark``: the batches get no mark;
+    the joined waveform is marked in one launch (``hip.wm_embed``), so the carrier's phase runs on across the segments and no cue
+    moves."""
     import torch
 
     from . import align as A
     from . import hip
+    from .watermark import check_mark
 
     step, inc = hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused before anything runs)
+    check_mark(watermark)
     if token_spans is not None and not callable(token_spans):
         raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
     spans_of = token_spans if token_spans is not None else (lambda t: A.token_spans(tts.tokenizer, t))
@@ -266,6 +270,8 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                 all_edges.append((s, e))
         base += offs[-1]
     wav = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).reshape(1, 1, -1)
+    if watermark is not None and wav.numel() > 0:
+        wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
     return LongformResult(wav, cues, groups, parts if keep_parts else None, all_edges if keep_parts else None, words)
 
 
@@ -274,15 +280,30 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                 max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                 fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0,
-                pitch: float = 0.0) -> Iterator[Any]:
-    """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``)."""
+                pitch: float = 0.0, watermark=None) -> Iterator[Any]:
+    """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``).
+    ``watermark``: every piece goes through one ``hip.WatermarkState`` (what is ready of it is yielded, nothing when that is empty)
+    and a last piece carries the flush."""
     from . import hip
+    from .watermark import check_mark
 
     hip.prosody_step(speed, pitch)
+    check_mark(watermark)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
         return
+    wms = hip.WatermarkState(1, watermark, tts.device) if watermark is not None else None
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
                        join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, pitch=pitch):
-        yield grp.piece.reshape(1, -1)
+        piece = grp.piece.reshape(1, -1)
+        if wms is None:
+            yield piece
+        elif piece.numel() > 0:
+            out, n = wms.feed(piece)
+            if n[0] > 0:
+                yield out[:, : n[0]]
+    if wms is not None:
+        out, n = wms.flush()
+        if n[0] > 0:
+            yield out[:, : n[0]]

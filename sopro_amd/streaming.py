@@ -39,23 +39,29 @@ class SoproTTSStreamer:
                ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None,
                nar_context_frames: Optional[int] = None, min_gen_frames: Optional[int] = None,
                text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0,
-               pitch: float = 0.0) -> Iterator[torch.Tensor]:
+               pitch: float = 0.0, watermark=None) -> Iterator[torch.Tensor]:
         """``speed`` (new): speaking rate in [0.5, 2.0].  Other than 1.0, every decoded chunk is fed to a ``hip.TimeStretchState``
         and the blocks that became ready are yielded as [1, n * 480] (a step that completes no block yields nothing); a flush
         after the last chunk yields the rest.  The concatenation is ``hip.time_stretch`` of the unstretched stream's
         concatenation, bit for bit.  ``pitch`` (new): semitones in [-12, 12].  Other than 0.0, the chunks (stretched at
         ``hip.prosody_step``'s step' where that is not the identity) are fed to a ``hip.PitchShiftState`` and the outputs whose
         taps are in are yielded as [1, n]; both states are flushed after the last chunk.  The concatenation is
-        ``hip.apply_prosody`` of the plain stream's concatenation, bit for bit."""
+        ``hip.apply_prosody`` of the plain stream's concatenation, bit for bit.  ``watermark`` (new): a ``sopro_amd.Watermark``.
+        The chunks (after the stretch and the resampler) are fed to a ``hip.WatermarkState`` and the 480-sample blocks whose
+        envelope is final are yielded; the state is flushed last.  The concatenation is ``hip.wm_embed`` of the unmarked stream's
+        concatenation, bit for bit."""
         from . import hip
+        from .watermark import check_mark
 
         tts = self.tts
+        check_mark(watermark)
         step, inc = hip.prosody_step(speed, pitch)
         tsm = hip.TimeStretchState(1, None, tts.device, steps=[step]) if step != hip.TSM_HS << 16 else None
         psh = hip.PitchShiftState(1, None, tts.device, incs=[inc]) if inc != hip.PITCH_ONE else None
+        wms = hip.WatermarkState(1, watermark, tts.device) if watermark is not None else None
 
         def rate(wav: Optional[torch.Tensor], last: bool = False) -> Optional[torch.Tensor]:
-            for st in (tsm, psh):  # (the stretch's flush feeds the resampler before that is flushed)
+            for st in (tsm, psh, wms):  # (a stage's flush feeds the next one before that is flushed)
                 if st is None or (wav is None and not last):
                     continue
                 out, n = st.feed(wav, flush=last)
@@ -104,7 +110,7 @@ class SoproTTSStreamer:
             wav = rate(refine_and_emit(len(hist)))
             if wav is not None:
                 yield wav
-        if tsm is not None or psh is not None:
+        if tsm is not None or psh is not None or wms is not None:
             wav = rate(None, last=True)
             if wav is not None:
                 yield wav
@@ -113,15 +119,17 @@ class SoproTTSStreamer:
 @torch.inference_mode()
 def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
            ref: Optional[PreparedReference] = None, chunk_frames: int = 6, cache_trim: str = "none", speed: float = 1.0,
-           pitch: float = 0.0, **kwargs) -> Iterator[torch.Tensor]:
-    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed`` and ``pitch`` are new: see MimiStreamDecoder,
-    SoproTTSStreamer.stream)"""
+           pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[torch.Tensor]:
+    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch`` and ``watermark`` are new: see
+    MimiStreamDecoder, SoproTTSStreamer.stream)"""
     from . import hip
+    from .watermark import check_mark
 
     hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused here, not at the first chunk)
+    check_mark(watermark)
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
-                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, **kwargs)
+                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
 
 
 def refuse_speed(speed, what: str) -> None:
@@ -139,6 +147,13 @@ def refuse_pitch(pitch, what: str) -> None:
 
     if hip.pitch_inc(pitch) != hip.PITCH_ONE:
         raise NotImplementedError(f"{what} has no pitch control (pitch={pitch!r}): use stream(), synthesize_batch() or "
+                                  "SynthesisService.submit() in mode='batch'")
+
+
+def refuse_watermark(watermark, what: str) -> None:
+    """The lockstep / frame-level paths have no watermark: anything but None is an error, never ignored."""
+    if watermark is not None:
+        raise NotImplementedError(f"{what} has no watermark (watermark={watermark!r}): use stream(), synthesize_batch() or "
                                   "SynthesisService.submit() in mode='batch'")
 
 
@@ -194,15 +209,16 @@ def stream_batch(tts, texts: Sequence[str], refs: Sequence, *, chunk_frames: int
                  nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                  phase_locks: Optional[tuple] = None, timings: Optional[Dict[str, float]] = None,
                  alive: Optional[Callable[[int], bool]] = None, speed: float = 1.0,
-                 pitch: float = 0.0) -> Iterator[List[Optional[torch.Tensor]]]:
+                 pitch: float = 0.0, watermark=None) -> Iterator[List[Optional[torch.Tensor]]]:
     """B utterances streamed in lockstep.  Yields, per step, a list of B entries: a [1, n * 1920] chunk or None.  Row b's non-None
     chunks are what ``stream(texts[b], ref=refs[b], seed=seeds[b], ...)`` yields: same chunk sizes, same stop rule (first EOS).
     ``seeds``: one per row (None: a fresh take for that row).  ``phase_locks`` = (AR lock, bulk lock): held around the AR advance and
     around refinement + decode of every step (a serving lane shares its device with whole-utterance batches).  ``timings``: seconds
     of host wall time accumulated under "ar", "refine", "decode".  ``alive(b)`` (a server): False once row b's consumer has gone - the
-    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0 (batched streams have neither control)."""
+    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0, ``watermark``: only None (batched streams have none of the three)."""
     refuse_speed(speed, "stream_batch")
     refuse_pitch(pitch, "stream_batch")
+    refuse_watermark(watermark, "stream_batch")
     model = tts.model
     B = len(texts)
     if B == 0 or len(refs) != B:

@@ -128,7 +128,7 @@ class SoproTTS:
                    ref_tokens_tq: Optional[torch.Tensor] = None, max_frames: int = 400, top_p: float = 0.9,
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
-                   seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0) -> torch.Tensor:
+                   seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
         draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed`` (new): speaking rate
@@ -136,9 +136,13 @@ class SoproTTS:
         ``pitch`` (new): semitones in [-12, 12], applied to the decoded waveform as a stretch by rho = 2^(pitch / 12) and a
         band-limited resample that reads rho times as fast (``hip.prosody_step``, ``hip.pitch_shift``): the duration stays what
         ``speed`` makes it and every frequency - formants included - is multiplied by rho; 0.0 launches nothing.  ``speed / rho``
-        must lie in [0.5, 2.0]."""
+        must lie in [0.5, 2.0].  ``watermark`` (new): a ``sopro_amd.Watermark`` (key, tag, strength) added to the waveform as the
+        last step, after rate and pitch (``hip.wm_embed``; see ``sopro_amd.watermark`` for what the mark survives); None launches
+        nothing."""
         from . import hip
+        from .watermark import check_mark
 
+        check_mark(watermark)
         step, inc = hip.prosody_step(speed, pitch)
         text_ids = self.encode_text(text)
         if ref is None:
@@ -148,10 +152,14 @@ class SoproTTS:
             style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
             min_gen_frames=min_gen_frames, seed=seed)
         wav = self.codec.decode_full(tokens)
-        if hip.is_plain([(step, inc)]) or wav.numel() == 0:
+        if wav.numel() == 0:
             return wav
-        out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
-        return out.reshape(1, 1, -1)
+        if not hip.is_plain([(step, inc)]):
+            out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
+            wav = out.reshape(1, 1, -1)
+        if watermark is not None:
+            wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
+        return wav
 
     @torch.inference_mode()
     def synthesize_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, max_frames: int = 400,
@@ -161,7 +169,8 @@ class SoproTTS:
                          phase_locks: Optional[tuple] = None, seed: Optional[int] = None, nonces: Optional[Sequence[int]] = None,
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
                          speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
-                         align_heads=None, pitch: Union[float, Sequence[float]] = 0.0) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         align_heads=None, pitch: Union[float, Sequence[float]] = 0.0,
+                         watermark=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
@@ -176,13 +185,19 @@ class SoproTTS:
         ``alignment``: a sink like ``timings`` - a list passed in is filled with one ``align.Alignment`` per row (frame -> text
         position path, frame range per position, confidence; in frames, before any stretch) by a post-pass on the bulk stream
         (``model.align_batch``: the AR stack replayed over the generated tokens, ``hip.align_scores`` / ``hip.align_paths``);
-        ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched."""
+        ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched.
+        ``watermark``: one ``sopro_amd.Watermark`` or None, or one per row with None entries allowed; the padded batch (stretched and
+        shifted where asked) is marked in one launch on the bulk stream before it is sliced (``hip.wm_embed``), so ``PaddedBatch.wav``
+        is marked.  All rows None: nothing is launched, and a row at None among marked ones comes back bit for bit."""
         import contextlib
         import time
 
         from . import hip
+        from .watermark import per_row
 
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
+        marks = per_row(watermark, len(ids))
+        marked = any(m is not None for m in marks)
         prosody = hip.prosody_steps(speed, pitch, len(ids))
         stretch = not hip.is_plain(prosody)  # (a rate, a pitch or both)
         if alignment is not None:
@@ -265,10 +280,12 @@ class SoproTTS:
             n_samples = [n * hop for n in lens]
             if stretch:  # (rows at 1.0 / 0.0 in a mixed batch come back bit for bit: both operators are the identity there)
                 wav, n_samples = hip.apply_prosody(wav, n_samples, prosody)
+            if marked:  # (last: the mark does not survive a stretch or a resample)
+                wav = hip.wm_embed(wav, n_samples, marks)
             toks = None
             if padded:  # (the engine's own token matrix: copied before the next pass overwrites it, complete before any stream reads it)
                 toks = codes.long()
-            if padded or stretch:
+            if padded or stretch or marked:
                 self.model.bulk_stream.synchronize()
         if padded:
             return PaddedBatch(wav, n_samples, toks, lens)
@@ -279,7 +296,7 @@ class SoproTTS:
                          ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
                          top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                          ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
-                         speed: float = 1.0, pitch: float = 0.0):
+                         speed: float = 1.0, pitch: float = 0.0, watermark=None):
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
@@ -288,10 +305,13 @@ class SoproTTS:
         ``align.stretch_cues`` at the stretch's own step and then ``align.shift_cues`` (+-240 / 2^(pitch / 12) samples: see there).
         ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
-        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12)."""
+        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12).  ``watermark``: as
+        in ``synthesize``; the mark changes no length, so the cues do not move."""
         from . import align as A
         from . import hip
+        from .watermark import check_mark
 
+        check_mark(watermark)
         step, inc = hip.prosody_step(speed, pitch)
         text_ids = self.encode_text(text)
         spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
@@ -313,43 +333,49 @@ class SoproTTS:
                 words = A.stretch_cues(words, step)
             if inc != hip.PITCH_ONE:
                 words = A.shift_cues(words, inc)
+        if watermark is not None and wav.numel() > 0:
+            wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
         return A.TimedResult(wav, words, sink[0])
 
     def clone_lane(self) -> "SoproTTS":
         """Another engine over the same device weights (own streams / scratch), for pipelining batches."""
         return SoproTTS(self.model.clone_lane(), self.cfg, self.tokenizer, self.codec.clone_lane(), str(self.device))
 
-    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, **kwargs) -> Iterator[torch.Tensor]:
+    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[torch.Tensor]:
         """reference: src/sopro/model.py:577-580.  ``speed`` (new): speaking rate in [0.5, 2.0]; every decoded chunk goes through
         the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream).
-        ``pitch`` (new): semitones in [-12, 12]; the chunks then also go through the chunked resampler and come out as [1, n]."""
+        ``pitch`` (new): semitones in [-12, 12]; the chunks then also go through the chunked resampler and come out as [1, n].
+        ``watermark`` (new): a ``sopro_amd.Watermark``; every chunk goes through a ``hip.WatermarkState`` last, so a chunk comes out
+        up to 1440 samples short and the rest follows (flushed at the end).  The concatenation is ``hip.wm_embed`` of the unmarked
+        stream's concatenation, bit for bit."""
         from .align import refuse_timing
         from .streaming import stream
 
         refuse_timing(kwargs, "stream")
-        return stream(self, text, speed=speed, pitch=pitch, **kwargs)
+        return stream(self, text, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
 
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
                      nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
-                     speed: float = 1.0, pitch: float = 0.0, **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
+                     speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
         entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
         A speaking rate or a pitch is not available here (``speed`` other than 1.0 or ``pitch`` other than 0.0 raises): use
-        ``stream`` or ``synthesize_batch``."""
+        ``stream`` or ``synthesize_batch``.  Neither is a watermark (``watermark`` other than None raises)."""
         from .align import refuse_timing
-        from .streaming import refuse_pitch, refuse_speed, stream_batch
+        from .streaming import refuse_pitch, refuse_speed, refuse_watermark, stream_batch
 
         refuse_timing(kwargs, "stream_batch")
         refuse_speed(speed, "stream_batch")
         refuse_pitch(pitch, "stream_batch")
+        refuse_watermark(watermark, "stream_batch")
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
                             cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, pitch=pitch,
                             **kwargs)
 
-    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, **kwargs):
+    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs):
         """New: a text of any length (a paragraph, an article, a chapter) -> ``LongformResult``: ``wav`` [1, 1, N] on the device and
         ``segments`` [(text, start sample, end sample)] in it.  The text is cut into sentences (``longform.split_text``,
         ``max_chars``), the voice is prepared once, groups of up to ``max_rows`` segments (``plan``: "throughput", "latency" or a
@@ -362,22 +388,35 @@ class SoproTTS:
         padded batch is stretched before the join (``parts`` are the stretched rows, cue times refer to the stretched audio) and
         the pauses are divided by it.  ``pitch``: semitones in [-12, 12]; every group's batch is stretched and resampled before the
         join (see ``synthesize``), the pauses are not touched by it.  ``word_cues=True`` also fills ``words`` (one ``align.LongWordCue`` per word, samples in the
-        joined waveform).  Full parameter list: ``longform.synthesize_long``."""
+        joined waveform).  ``watermark``: a ``sopro_amd.Watermark``; the batches run unmarked and the joined waveform is marked in one
+        launch, so the carrier's phase is continuous across the segments (``parts`` stay unmarked).  Full parameter list:
+        ``longform.synthesize_long``."""
         from .longform import synthesize_long
 
-        return synthesize_long(self, text, speed=speed, pitch=pitch, **kwargs)
+        return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
 
-    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, **kwargs) -> Iterator[torch.Tensor]:
+    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[torch.Tensor]:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
-        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed`` and ``pitch``)."""
+        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed`` and ``pitch``).
+        ``watermark``: the pieces go through one ``hip.WatermarkState`` (a piece comes out up to 1440 samples short, the rest follows,
+        and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit."""
         from . import hip
         from .align import refuse_timing
         from .longform import stream_long
+        from .watermark import check_mark
 
         refuse_timing(kwargs, "stream_long")
         hip.prosody_step(speed, pitch)  # (refused here, not at the first piece)
-        return stream_long(self, text, speed=speed, pitch=pitch, **kwargs)
+        check_mark(watermark)
+        return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
+
+    def detect_watermark(self, wav, key: int):
+        """New: does ``wav`` carry the mark of ``key``?  -> ``watermark.WatermarkResult(present, score, tag, offset, z_sync, z_tag)``,
+        or a list of them for a list of clips (``watermark.detect`` on this engine's device)."""
+        from .watermark import detect
+
+        return detect(wav, key, device=self.device)
 
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""

@@ -1001,6 +1001,56 @@ int sopro_wm_fold_rows_f32(const float* in, int64_t in_stride, const int32_t* in
 int sopro_wm_corr_rows_f32(const float* f, const int8_t* dtab, int32_t n_keys, const int32_t* key_idx, int32_t rows, float* R, void* stream);
 int sopro_wm_peak_rows_f32(const float* R, int32_t rows, int32_t* out, void* stream);
 
+/* ---- silence control: no pause longer than a cap, no silent lead-in, a short tail -------------------------------------------- */
+/* No reference counterpart.  24 kHz mono fp32 rows of a padded batch.  Every fp32 product and sum is rounded on its own (no
+ * contraction) and the library evaluates no trigonometry, so the operator has one right answer, bit for bit (tests/sil_ref.py
+ * restates both forms in numpy; DESIGN.md "Silence control" gives the rationale).
+ *   HOP = 240 samples (10 ms).  tab[m] = fl32(0.5 - 0.5 cos(pi (m + 0.5) / HOP)), m < HOP, made by the host in float64.
+ *   Per row: thr > 0 (absolute amplitude), cap_h (the longest pause left in, in hops), b (the onset guard, in hops), 1 <= b <= 16,
+ *   b + 1 <= cap_h <= 1000, a = cap_h - b.  cap_h == 0: the row is copied, bit for bit.  Any other value out of range: the row is
+ *   refused (out_lens = -1).
+ * Definition for a row x[0 .. L).  Hop j covers [j HOP, min((j + 1) HOP, L)) and is active iff max |x| over it is >= thr (a NaN
+ *   compares false).  A run is a maximal stretch [j0, j1) of inactive hops, n = j1 - j0.  A row without an active hop (L == 0
+ *   included) comes out empty, with the one cut (0, L) when L > 0.  Otherwise every hop is copied, except:
+ *   leading run (j0 == 0), n > b + 1: hops [0, j1 - b - 1) are removed, hop j1 - b - 1 is faded in, y[i] = fl32(x[i] * tab[i]), hops
+ *     [j1 - b, j1) follow whole.  Cut (0, (j1 - b - 1) HOP).
+ *   interior run, n > cap_h: with p = j0 + a, q = j1 - b, hops [j0, p - 1) stay, then one crossfade hop
+ *     y[i] = fl32(fl32(x[(p - 1) HOP + i] * tab[HOP - 1 - i]) + fl32(x[(q - 1) HOP + i] * tab[i])), then hops [q, j1): the run is
+ *     cap_h hops long.  Cut (p HOP, (q - p) HOP).
+ *   trailing run (j1 is the number of hops), n > a: hops [j0, j0 + a - 1) stay, hop j0 + a - 1 is faded out, fl32(x * tab[HOP - 1 - i]),
+ *     the rest is removed.  Cut ((j0 + a) HOP, L - (j0 + a) HOP).  n <= a: unchanged, a partial last hop included.
+ * Outputs per row: out[row, 0 .. out_lens[row]); n_cuts[row] and cuts int32 [rows][cuts_cap][2] = (source position, samples
+ *   removed) in order - the exact map for cues (a position inside a removed range maps to the cut's start).  Nothing at or past
+ *   out_cap or past out_lens[row] is written; a row whose output, cuts or parameters do not fit gets out_lens[row] = -1, nothing
+ *   written, n_cuts 0 and (chunked) a zeroed state.
+ * Chunked form (same numbers): `state` holds, per row, whether speech has been seen, the current run length, samples received and
+ *   emitted, and a retained tail: hop a - 1 of the current run where its fate is open, the last b + 1 inactive hops after it (before
+ *   speech: the last b + 1 hops), and the incomplete hop - at most 18 hops and 239 samples <= SOPRO_SIL_TAIL.  A call appends
+ *   in[row, 0 .. in_lens[row]) and emits what is decided: active hops at once, the first a - 1 hops of a run at once, the rest of a
+ *   run when speech resumes; `flush` decides the partial last hop and the trailing run and zeroes the row's state.  Any chunking
+ *   followed by a flush gives the one-shot result bit for bit, cuts included: the cuts of a call are those decided in it, in the
+ *   row's total source coordinates.  sopro_sil_chunk_out_cap(in_cap) = in_cap + SOPRO_SIL_TAIL bounds the output of one call.
+ *   in_lens int32 [rows] (clamped to [0, in_cap]), thr float [rows], cap_h / b int32 [rows], tab float [HOP], out_lens / n_cuts
+ *   int32 [rows]: device memory.  state: NULL for a one-shot call (flush must be set), else sopro_sil_state_bytes(rows) bytes of
+ *   device memory, zeroed before a row's first chunk.  workspace: sopro_sil_ws_bytes(rows, in_cap) bytes of device memory for a
+ *   one-shot call, sopro_sil_ws_bytes(rows, sopro_sil_chunk_out_cap(in_cap)) with a state (the activity bitmap, the segment table).
+ *   Rows need no alignment beyond 4 bytes (16-byte copies are used where a row's source and destination allow them); `out` must not
+ *   overlap `in`.  sopro_sil_rows_f32 enqueues three launches on `stream` - hop activity as one 64-bit word per 64 hops; one workgroup
+ *   per row from the bitmap to the cuts and the segment table (one-shot: a lane per word, looping when a row has more than
+ *   SOPRO_SIL_PLAN_WORDS words; chunked: the hop-level state machine, sequential over the call's bits); a gather over (tile of
+ *   SOPRO_SIL_TILE outputs, row) - and with a state a fourth, small one that rewrites it; it allocates nothing and synchronises
+ *   nothing. */
+#define SOPRO_SIL_HOP 240
+#define SOPRO_SIL_TAIL 4608
+#define SOPRO_SIL_TILE 2048
+#define SOPRO_SIL_PLAN_WORDS 64
+int64_t sopro_sil_state_bytes(int32_t rows);
+int64_t sopro_sil_chunk_out_cap(int64_t in_cap);
+int64_t sopro_sil_ws_bytes(int32_t rows, int64_t max_len);
+int sopro_sil_rows_f32(const float* in, int64_t in_stride, const int32_t* in_lens, int64_t in_cap, const float* thr, const int32_t* cap_h,
+                       const int32_t* b, int32_t rows, void* state, int32_t flush, const float* tab, void* workspace, float* out,
+                       int64_t out_stride, int64_t out_cap, int32_t* out_lens, int32_t* cuts, int32_t cuts_cap, int32_t* n_cuts, void* stream);
+
 /* ---- word timestamps: attention maps of the AR text cross-attention and the best monotonic path through them -------------- */
 /* No reference counterpart (the reference never materialises attention weights).  Definition: DESIGN.md "Word timestamps";
  * numpy / torch restatement: tests/align_ref.py.

@@ -161,6 +161,27 @@ def shift_cues(cues: Sequence[WordCue], inc: int) -> List[WordCue]:
     return [c._replace(start_sample=map_pitch(c.start_sample, inc), end_sample=map_pitch(c.end_sample, inc)) for c in cues]
 
 
+def map_cuts(sample: int, cuts: Sequence[Tuple[int, int]]) -> int:
+    """A sample position before the silence operator -> after it, by the operator's own cut table (``hip.silence_squeeze``: (source
+    position, samples removed) in order).  Exact: a position at or past the end of a removed range moves up by what was removed
+    before it, a position inside a removed range maps to the cut's start."""
+    s, off = int(sample), 0
+    for pos, n in cuts:
+        if s >= pos + n:
+            off += n
+        elif s > pos:
+            return int(pos) - off
+        else:
+            break
+    return s - off
+
+
+def squeeze_cues(cues: Sequence[WordCue], cuts: Sequence[Tuple[int, int]]) -> List[WordCue]:
+    """Cues of the waveform that went into the silence operator -> cues of what came out (after ``stretch_cues`` / ``shift_cues``:
+    the operator runs last before the watermark)."""
+    return [c._replace(start_sample=map_cuts(c.start_sample, cuts), end_sample=map_cuts(c.end_sample, cuts)) for c in cues]
+
+
 def long_cue(cue: WordCue, segment: int, off: int, edge_start: int, edge_end: int) -> LongWordCue:
     """A segment's cue in the joined waveform: ``off + (sample - edge_start)``, the sample clamped to the kept range
     [edge_start, edge_end] of the segment first (what the join trimmed away holds no word)."""

@@ -282,6 +282,10 @@ SYMBOLS = {
     "sopro_wm_fold_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _p, _p]),
     "sopro_wm_corr_rows_f32": (C.c_int, [_p, _p, _i32, _p, _i32, _p, _p]),
     "sopro_wm_peak_rows_f32": (C.c_int, [_p, _i32, _p, _p]),
+    "sopro_sil_state_bytes": (_i64, [_i32]),
+    "sopro_sil_chunk_out_cap": (_i64, [_i64]),
+    "sopro_sil_ws_bytes": (_i64, [_i32, _i64]),
+    "sopro_sil_rows_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i32, _p, _p, _p, _i64, _i64, _p, _p, _i32, _p, _p]),
     "sopro_align_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "sopro_align_scores_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, C.c_uint32, _f32, _i32, _p, _i64,
                                          _i64, _p]),
@@ -1532,6 +1536,127 @@ def wm_detect_rows(wav: torch.Tensor, lens, keys, *, details: bool = False):
     z = host[:, 2:].contiguous().view(torch.float32).tolist()
     res = [wm.result_of(o[b][0], o[b][1], z[b][0], z[b][1]) for b in range(rows)]
     return (res, f, R) if details else res
+
+
+# ---- silence control (sopro_sil_*; definition in include/sopro_hip.h, numpy restatement in tests/sil_ref.py; parameters in silence.py) ----
+SIL_HOP, SIL_TAIL, SIL_TILE, SIL_PLAN_WORDS = 240, 4608, 2048, 64
+sil_calls = 0  # calls of sopro_sil_rows_f32 by this process: the silence=None paths never add to it
+
+
+def _sil_cuts_cap(lens_h, sils) -> int:
+    """Cuts a row can have: one per cap_h + 2 hops (a run longer than the cap and the active hop that ends it), the leading and the
+    trailing one."""
+    return max((-(-n // SIL_HOP)) // (s.cap_hops + 2) + 2 if s is not None else 0 for n, s in zip(lens_h, sils))
+
+
+def _sil_launch(wav, in_cap: int, lens_h, tot_h, sils, state, flush: bool, out):
+    """One sopro_sil_rows_f32 on the current stream and one host copy of what it found -> (out_lens, cuts per row as (source
+    position, samples removed) tuples).  ``tot_h``: the samples a row can hold cuts for (a chunked row: everything received)."""
+    global sil_calls
+    import numpy as np
+
+    rows = len(lens_h)
+    dev = out.device
+    lib = load()
+    with torch.cuda.device(dev):
+        thr_bits = np.array([s.thr if s is not None else 1.0 for s in sils], dtype=np.float32).view(np.int32).tolist()
+        args = torch.tensor([lens_h, [s.cap_hops if s is not None else 0 for s in sils], [s.onset_hops if s is not None else 1 for s in sils],
+                             thr_bits], dtype=torch.int32).to(dev)  # one upload
+        cuts_cap = max(1, _sil_cuts_cap(tot_h, sils))
+        vcap = int(in_cap) if state is None else int(lib.sopro_sil_chunk_out_cap(int(in_cap)))
+        ws = torch.empty(max(1, int(lib.sopro_sil_ws_bytes(rows, vcap)) // 8), dtype=torch.int64, device=dev)
+        res = torch.empty(rows * (2 + 2 * cuts_cap), dtype=torch.int32, device=dev)  # out_lens | n_cuts | cuts: one download
+        out_lens, n_cuts, cuts = res[:rows], res[rows: 2 * rows], res[2 * rows:]
+        sil_calls += 1
+        _check(lib.sopro_sil_rows_f32(ptr(wav) if in_cap > 0 else None, int(wav.stride(0)) if in_cap > 0 else 0, args[0].data_ptr(), int(in_cap),
+                                      args[3].data_ptr(), args[1].data_ptr(), args[2].data_ptr(), rows,
+                                      state.data_ptr() if state is not None else None, int(bool(flush)), ptr(fade_table(SIL_HOP, dev)),
+                                      ws.data_ptr(), ptr(out), int(out.stride(0)), int(out.shape[1]), out_lens.data_ptr(), cuts.data_ptr(),
+                                      cuts_cap, n_cuts.data_ptr(), _stream()), "sopro_sil_rows_f32")
+        host = res.cpu()
+    got = host[:rows].tolist()
+    nc = host[rows: 2 * rows].tolist()
+    table = host[2 * rows:].reshape(rows, cuts_cap, 2).tolist()
+    return got, [[(int(p), int(n)) for p, n in table[r][: nc[r]]] for r in range(rows)]
+
+
+def silence_squeeze(wav: torch.Tensor, lens, sils, *, out: Optional[torch.Tensor] = None):
+    """Silence control on the rows of a padded batch (sopro_sil_rows_f32, one-shot form): ``wav`` fp32 [rows, >= max(lens)] on the
+    device (rows ``wav.stride(0)`` apart, any alignment), ``lens`` valid samples per row, ``sils`` one ``Silence`` or None, or one
+    per row -> (out [rows, max(out_lens)], out_lens, cuts): row b valid for out_lens[b] samples, cuts[b] its (source position,
+    samples removed) pairs in order (``align.map_cuts``).  A row whose ``Silence`` is None comes back bit for bit, without cuts.
+    Three launches on the current stream and one small host copy (the lengths and the cuts).  ``out``: a [rows, >= max(lens)] fp32
+    buffer to write into; it must not overlap ``wav``.  All None: nothing is launched and ``wav[:, :max(lens)]`` is returned as it is."""
+    from . import silence as S
+
+    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    rows = len(lens_h)
+    _tsm_check_rows(wav, lens_h, "silence_squeeze")
+    sils = S.per_row(sils, rows, "sils")
+    cap = max(lens_h, default=0)
+    if out is not None:
+        ptr(out)
+        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
+            raise SoproHipError(f"silence_squeeze: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+    if rows == 0 or all(s is None for s in sils):
+        if out is None:
+            return wav[:, :cap], lens_h, [[] for _ in range(rows)]
+        out[:, :cap].copy_(wav[:, :cap])  # (a caller that asked for its own buffer gets the rows there)
+        return out[:, :cap], lens_h, [[] for _ in range(rows)]
+    if out is None:
+        out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=wav.device)
+    got, cuts = _sil_launch(wav, int(wav.shape[1]), lens_h, lens_h, sils, None, True, out)
+    if min(got) < 0:
+        raise SoproHipError("silence_squeeze: a row's samples or cuts did not fit")
+    return out[:, : max(got)], got, cuts
+
+
+class SilenceState:
+    """Chunked form of ``silence_squeeze`` for ``rows`` streams: ``feed`` appends a chunk per row and returns what is decided (sound
+    at once, the first hops of a pause at once, the rest of a pause when sound resumes), ``flush`` the rest.  Any chunking followed by
+    ``flush`` gives the one-shot result bit for bit.  The state (speech seen, run length, samples received and emitted, a retained
+    tail of at most 18 hops and 239 samples per row) lives on the device; every call is four launches and one small host copy.
+    ``cuts[b]`` collects row b's cuts, in the row's total source coordinates, until the flush that ends the row."""
+
+    def __init__(self, rows: int, sils, device):
+        from . import silence as S
+
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError("rows >= 1")
+        self.sils = S.per_row(sils, self.rows, "sils")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise SoproHipError("SilenceState lives on a HIP device: the Sopro hot path has no CPU fallback")
+        self.state = torch.zeros(int(load().sopro_sil_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
+        self.recv = [0] * self.rows
+        self.cuts: List[list] = [[] for _ in range(self.rows)]
+        self._ended = False
+
+    def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False):
+        """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
+        if self._ended:  # (the first call after a flush starts new rows)
+            self.recv, self.cuts, self._ended = [0] * self.rows, [[] for _ in range(self.rows)], False
+        if wav is None:
+            n, lens_h = 0, [0] * self.rows
+        else:
+            n = int(wav.shape[-1])
+            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            _tsm_check_rows(wav, lens_h, "SilenceState.feed")
+        self.recv = [a + b for a, b in zip(self.recv, lens_h)]
+        cap = int(load().sopro_sil_chunk_out_cap(n))
+        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        got, cuts = _sil_launch(wav, n, lens_h, self.recv, self.sils, self.state, flush, out)
+        if min(got) < 0:
+            raise SoproHipError("SilenceState: a row's samples or cuts did not fit")
+        for b in range(self.rows):
+            self.cuts[b] += cuts[b]
+        self._ended = bool(flush)
+        return out[:, : max(got)], got
+
+    def flush(self):
+        """The remaining samples (the partial last hop and the trailing run are decided); the state is fresh afterwards."""
+        return self.feed(None, flush=True)
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

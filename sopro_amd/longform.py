@@ -182,12 +182,13 @@ class _Group(NamedTuple):
 
 
 def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top_p, temperature, anti_loop, style_strength, min_gen_frames,
-            seed, pauses_ms, join_kw, speed=1.0, word_cues=False, align_heads=None, pitch=0.0) -> Iterator[_Group]:
+            seed, pauses_ms, join_kw, speed=1.0, word_cues=False, align_heads=None, pitch=0.0, silence=None) -> Iterator[_Group]:
     """Run the groups in order: one ``synthesize_batch`` and one ``hip.join_segments`` each, straight from the decoder's padded
     batch.  Segment k of the text draws with nonce (seed + k) & 0xFFFFFFFF and row id 0 - the sampler stream
     ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce.  ``speed``: the
     batch comes back stretched (rows in parallel, before the join: trimming, fades and cue times then refer to the audio as it is
-    heard) and the pauses shrink or grow with it.  ``pitch``: the batch comes back shifted as well; the pauses follow ``speed`` only."""
+    heard) and the pauses shrink or grow with it.  ``pitch``: the batch comes back shifted as well; the pauses follow ``speed`` only.
+    ``silence``: the batch comes back squeezed (``batch.cuts``); the operator never sees the pauses the join adds."""
     from . import hip
 
     n = len(segs)
@@ -200,7 +201,7 @@ def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top
         batch = tts.synthesize_batch([s.text for s in segs[k0: k0 + g]], [ref] * g, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                      anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed,
                                      nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, speed=speed, alignment=sink,
-                                     align_heads=align_heads, pitch=pitch)
+                                     align_heads=align_heads, pitch=pitch, silence=silence)
         piece, edges, offs = hip.join_segments(batch.wav, batch.lens, gaps[k0: k0 + g], **join_kw)
         yield _Group(k0, piece, edges, offs, batch, sink)
         k0 += g
@@ -220,7 +221,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
                     keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None,
-                    pitch: float = 0.0, watermark=None) -> LongformResult:
+                    pitch: float = 0.0, watermark=None, silence=None) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
     (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k; at a ``speed`` other than 1.0 the
@@ -228,15 +229,18 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     and ``align.shift_cues``).  ``token_spans``: a callable text -> [(start, end)] per token id for tokenizers
     that give no character offsets; ``align_heads``: the (layer, head) pairs to average.  ``watermark``: the batches get no mark;
     the joined waveform is marked in one launch (``hip.wm_embed``), so the carrier's phase runs on across the segments and no cue
-    moves."""
+    moves.  ``silence``: a ``sopro_amd.Silence``; every group's batch is squeezed before the join, so the join's own sentence gaps
+    are untouched, and a word cue goes through ``align.squeeze_cues`` with its row's cut table before ``align.long_cue``."""
     import torch
 
     from . import align as A
     from . import hip
+    from .silence import check_silence
     from .watermark import check_mark
 
     step, inc = hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused before anything runs)
     check_mark(watermark)
+    check_silence(silence)
     if token_spans is not None and not callable(token_spans):
         raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
     spans_of = token_spans if token_spans is not None else (lambda t: A.token_spans(tts.tokenizer, t))
@@ -251,7 +255,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
                        join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, word_cues=word_cues, align_heads=align_heads,
-                       pitch=pitch):
+                       pitch=pitch, silence=silence):
         pieces.append(grp.piece)
         offs, edges = grp.offs.tolist(), grp.edges.tolist()
         for i, (s, e) in enumerate(edges):
@@ -263,6 +267,8 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     wc = A.stretch_cues(wc, step)
                 if inc != hip.PITCH_ONE:
                     wc = A.shift_cues(wc, inc)
+                if grp.batch.cuts is not None:
+                    wc = A.squeeze_cues(wc, grp.batch.cuts[i])
                 words.extend(A.long_cue(c, grp.first + i, base + offs[i], s, e) for c in wc)
             if keep_parts:
                 n = grp.batch.lens[i]
@@ -280,22 +286,24 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                 max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                 fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0,
-                pitch: float = 0.0, watermark=None) -> Iterator[Any]:
+                pitch: float = 0.0, watermark=None, silence=None) -> Iterator[Any]:
     """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``).
     ``watermark``: every piece goes through one ``hip.WatermarkState`` (what is ready of it is yielded, nothing when that is empty)
-    and a last piece carries the flush."""
+    and a last piece carries the flush.  ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
     from . import hip
+    from .silence import check_silence
     from .watermark import check_mark
 
     hip.prosody_step(speed, pitch)
     check_mark(watermark)
+    check_silence(silence)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
         return
     wms = hip.WatermarkState(1, watermark, tts.device) if watermark is not None else None
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, pitch=pitch):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, pitch=pitch, silence=silence):
         piece = grp.piece.reshape(1, -1)
         if wms is None:
             yield piece

@@ -35,6 +35,7 @@ class _Request:
     speed: float = 1.0  # speaking rate of this request: applied after decoding, so it is no part of the batching key
     pitch: float = 0.0  # semitones of this request: applied after decoding too
     watermark: Any = None  # the mark of this request: applied last, one per row
+    silence: Any = None  # the silence control of this request: applied after rate and pitch, one per row
 
 
 class _StreamSink:
@@ -119,17 +120,20 @@ class SynthesisService:
     # ------------------------------------------------------------------ client side
     def submit(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
                anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
-               text_ids: Optional[torch.Tensor] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None,
+               text_ids: Optional[torch.Tensor] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
                **timing) -> "Future[torch.Tensor]":
         """Queue one utterance; the future resolves to the waveform ``[1, 1, N]`` on the device (``synthesize``'s result).
         ``speed``: speaking rate in [0.5, 2.0] of this request (``mode="batch"`` only).  It is applied to the decoded batch, one
         rate per row, so requests with different rates share a batch.  ``pitch``: semitones in [-12, 12] of this request, likewise
         (``mode="batch"`` only, one pitch per row, no part of the batching key).  ``watermark``: a ``sopro_amd.Watermark`` for this
-        request (``mode="batch"`` only; the batch is marked in one launch, one mark per row, so tenants share a batch).  The service has no word timing in either mode: a timing
+        request (``mode="batch"`` only; the batch is marked in one launch, one mark per row, so tenants share a batch).  ``silence``: a ``sopro_amd.Silence`` for this
+        request (``mode="batch"`` only; the batch is squeezed in one launch sequence, one setting per row, no part of the batching
+        key).  The service has no word timing in either mode: a timing
         keyword (``alignment``, ``word_cues``, ...) raises."""
         from . import hip
         from .align import refuse_timing
-        from .streaming import refuse_pitch, refuse_speed, refuse_watermark
+        from .silence import check_silence
+        from .streaming import refuse_pitch, refuse_silence, refuse_speed, refuse_watermark
         from .watermark import check_mark
 
         refuse_timing(timing, f"SynthesisService(mode={'continuous' if self.engine is not None else 'batch'!r})")
@@ -139,10 +143,12 @@ class SynthesisService:
             raise RuntimeError("service is closed")
         hip.prosody_step(speed, pitch)
         check_mark(watermark)
+        check_silence(silence)
         if self.engine is not None:
             refuse_speed(speed, "SynthesisService(mode='continuous')")
             refuse_pitch(pitch, "SynthesisService(mode='continuous')")
             refuse_watermark(watermark, "SynthesisService(mode='continuous')")
+            refuse_silence(silence, "SynthesisService(mode='continuous')")
             self.stats["requests"] += 1
             return self.engine.submit(text=text, text_ids=text_ids, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                       anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames)
@@ -152,26 +158,29 @@ class SynthesisService:
         ss = float(style_strength if style_strength is not None else self.tts.cfg.style_strength)
         key = (int(max_frames), float(top_p), float(temperature), bool(anti_loop), ss, min_gen_frames)
         fut: Future = Future()
-        self._inbox.put(_Request(ids, ref, key, fut, time.perf_counter(), speed=float(speed), pitch=float(pitch), watermark=watermark))
+        self._inbox.put(_Request(ids, ref, key, fut, time.perf_counter(), speed=float(speed), pitch=float(pitch), watermark=watermark,
+                                 silence=silence))
         return fut
 
     def submit_stream(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
                       anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                       text_ids: Optional[torch.Tensor] = None, chunk_frames: int = 6, cache_trim: str = "none",
                       nar_context_frames: Optional[int] = None, seed: Optional[int] = None, speed: float = 1.0,
-                      pitch: float = 0.0, watermark=None) -> Iterator[torch.Tensor]:
+                      pitch: float = 0.0, watermark=None, silence=None) -> Iterator[torch.Tensor]:
         """Queue one streamed utterance -> a blocking iterator over its [1, n * 1920] chunks (``stream``'s chunks).  Streams with equal
         parameters are grouped into batches of up to ``max_batch`` rows (within ``max_wait_ms``) and each batch runs as one
         ``stream_batch`` on a lane, sharing the device with whole-utterance batches (AR lock per chunk, bulk lock for refinement and
         decoding).  Closing or dropping the iterator drops the row from its batch.  Batched streams have no speaking-rate control:
-        ``speed`` other than 1.0 raises, and so do ``pitch`` other than 0.0 and ``watermark`` other than None."""
-        from .streaming import refuse_pitch, refuse_speed, refuse_watermark
+        ``speed`` other than 1.0 raises, and so do ``pitch`` other than 0.0, ``watermark`` other than None and ``silence`` other than
+        None."""
+        from .streaming import refuse_pitch, refuse_silence, refuse_speed, refuse_watermark
 
         if self._closed:
             raise RuntimeError("service is closed")
         refuse_speed(speed, "submit_stream")
         refuse_pitch(pitch, "submit_stream")
         refuse_watermark(watermark, "submit_stream")
+        refuse_silence(silence, "submit_stream")
         if self.engine is not None:
             raise RuntimeError("submit_stream is not available in mode='continuous' (frame-level admission has no streaming path); "
                                "use mode='batch'")
@@ -191,20 +200,23 @@ class SynthesisService:
                     anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0,
                     keep_ms: float = 30.0, fade_ms: float = 5.0, keep_parts: bool = False, speed: float = 1.0,
-                    pitch: float = 0.0, watermark=None) -> "Future":
+                    pitch: float = 0.0, watermark=None, silence=None) -> "Future":
         """Queue a text of any length -> a future of ``longform.LongformResult`` (``SoproTTS.synthesize_long``'s result).  The text is
         split here and every segment goes through ``submit``, so the scheduler batches the segments with whatever else is queued;
         a small waiter thread gathers the segment futures in order, stacks them into one padded tensor and joins them on the
         device (``hip.join_segments``).  The sampler draws as ``submit`` draws (a fresh take per segment: no seed, no group plan).
         ``speed``: every segment is submitted at this rate (stretched in its batch, before the join) and the pauses are divided by it.
         ``pitch``: every segment is submitted at this pitch; the pauses are not touched by it.  ``watermark``: the segments are
-        submitted unmarked and the joined waveform is marked (``hip.wm_embed``), as in ``SoproTTS.synthesize_long``."""
+        submitted unmarked and the joined waveform is marked (``hip.wm_embed``), as in ``SoproTTS.synthesize_long``.  ``silence``:
+        every segment is submitted with it (squeezed in its batch, before the join)."""
         from . import hip
         from .longform import LongformPart, LongformResult, join_params, pause_samples, scaled_pause, split_text
+        from .silence import check_silence
         from .watermark import check_mark
 
         hip.prosody_step(speed, pitch)
         check_mark(watermark)
+        check_silence(silence)
 
         if self._closed:
             raise RuntimeError("service is closed")
@@ -214,7 +226,7 @@ class SynthesisService:
         gaps = [scaled_pause(pause_samples(s.boundary, pauses_ms), speed) for s in segs]
         join_kw = join_params(trim_db, keep_ms, fade_ms)
         futs = [self.submit(s.text, ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
-                            style_strength=style_strength, min_gen_frames=min_gen_frames, speed=speed, pitch=pitch) for s in segs]
+                            style_strength=style_strength, min_gen_frames=min_gen_frames, speed=speed, pitch=pitch, silence=silence) for s in segs]
         done: Future = Future()
         dev = self.tts.device
 
@@ -316,7 +328,7 @@ class SynthesisService:
                     out = lane.synthesize_batch([""] * len(batch), [r.ref for r in batch], max_frames=mf, top_p=top_p, temperature=temp,
                                                 anti_loop=anti, style_strength=ss, min_gen_frames=mg, text_ids=[r.text_ids for r in batch],
                                                 phase_locks=locks, speed=[r.speed for r in batch], pitch=[r.pitch for r in batch],
-                                                watermark=[r.watermark for r in batch])
+                                                watermark=[r.watermark for r in batch], silence=[r.silence for r in batch])
                     self.stats["requests"] += len(batch)
                     self.stats["batches"] += 1
                     self.stats["rows"] += len(batch)

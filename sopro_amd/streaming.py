@@ -39,7 +39,7 @@ class SoproTTSStreamer:
                ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None,
                nar_context_frames: Optional[int] = None, min_gen_frames: Optional[int] = None,
                text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0,
-               pitch: float = 0.0, watermark=None) -> Iterator[torch.Tensor]:
+               pitch: float = 0.0, watermark=None, silence=None) -> Iterator[torch.Tensor]:
         """``speed`` (new): speaking rate in [0.5, 2.0].  Other than 1.0, every decoded chunk is fed to a ``hip.TimeStretchState``
         and the blocks that became ready are yielded as [1, n * 480] (a step that completes no block yields nothing); a flush
         after the last chunk yields the rest.  The concatenation is ``hip.time_stretch`` of the unstretched stream's
@@ -49,19 +49,25 @@ class SoproTTSStreamer:
         ``hip.apply_prosody`` of the plain stream's concatenation, bit for bit.  ``watermark`` (new): a ``sopro_amd.Watermark``.
         The chunks (after the stretch and the resampler) are fed to a ``hip.WatermarkState`` and the 480-sample blocks whose
         envelope is final are yielded; the state is flushed last.  The concatenation is ``hip.wm_embed`` of the unmarked stream's
-        concatenation, bit for bit."""
+        concatenation, bit for bit.  ``silence`` (new): a ``sopro_amd.Silence``.  The chunks (after the stretch and the
+        resampler, before the watermark) are fed to a ``hip.SilenceState``: the silent lead-in is never yielded, sound is yielded at
+        once, the end of a long pause when sound resumes; the state is flushed after the last chunk.  The concatenation is
+        ``hip.silence_squeeze`` of the plain stream's concatenation, bit for bit."""
         from . import hip
+        from .silence import check_silence
         from .watermark import check_mark
 
         tts = self.tts
         check_mark(watermark)
+        check_silence(silence)
         step, inc = hip.prosody_step(speed, pitch)
         tsm = hip.TimeStretchState(1, None, tts.device, steps=[step]) if step != hip.TSM_HS << 16 else None
         psh = hip.PitchShiftState(1, None, tts.device, incs=[inc]) if inc != hip.PITCH_ONE else None
+        sil = hip.SilenceState(1, silence, tts.device) if silence is not None else None
         wms = hip.WatermarkState(1, watermark, tts.device) if watermark is not None else None
 
         def rate(wav: Optional[torch.Tensor], last: bool = False) -> Optional[torch.Tensor]:
-            for st in (tsm, psh, wms):  # (a stage's flush feeds the next one before that is flushed)
+            for st in (tsm, psh, sil, wms):  # (a stage's flush feeds the next one before that is flushed)
                 if st is None or (wav is None and not last):
                     continue
                 out, n = st.feed(wav, flush=last)
@@ -110,7 +116,7 @@ class SoproTTSStreamer:
             wav = rate(refine_and_emit(len(hist)))
             if wav is not None:
                 yield wav
-        if tsm is not None or psh is not None or wms is not None:
+        if tsm is not None or psh is not None or sil is not None or wms is not None:
             wav = rate(None, last=True)
             if wav is not None:
                 yield wav
@@ -119,17 +125,19 @@ class SoproTTSStreamer:
 @torch.inference_mode()
 def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
            ref: Optional[PreparedReference] = None, chunk_frames: int = 6, cache_trim: str = "none", speed: float = 1.0,
-           pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[torch.Tensor]:
-    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch`` and ``watermark`` are new: see
+           pitch: float = 0.0, watermark=None, silence=None, **kwargs) -> Iterator[torch.Tensor]:
+    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch``, ``watermark`` and ``silence`` are new: see
     MimiStreamDecoder, SoproTTSStreamer.stream)"""
     from . import hip
+    from .silence import check_silence
     from .watermark import check_mark
 
     hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused here, not at the first chunk)
     check_mark(watermark)
+    check_silence(silence)
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
-                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
+                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
 
 def refuse_speed(speed, what: str) -> None:
@@ -154,6 +162,13 @@ def refuse_watermark(watermark, what: str) -> None:
     """The lockstep / frame-level paths have no watermark: anything but None is an error, never ignored."""
     if watermark is not None:
         raise NotImplementedError(f"{what} has no watermark (watermark={watermark!r}): use stream(), synthesize_batch() or "
+                                  "SynthesisService.submit() in mode='batch'")
+
+
+def refuse_silence(silence, what: str) -> None:
+    """The lockstep / frame-level paths have no silence control: anything but None is an error, never ignored."""
+    if silence is not None:
+        raise NotImplementedError(f"{what} has no silence control (silence={silence!r}): use stream(), synthesize_batch() or "
                                   "SynthesisService.submit() in mode='batch'")
 
 
@@ -209,16 +224,17 @@ def stream_batch(tts, texts: Sequence[str], refs: Sequence, *, chunk_frames: int
                  nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                  phase_locks: Optional[tuple] = None, timings: Optional[Dict[str, float]] = None,
                  alive: Optional[Callable[[int], bool]] = None, speed: float = 1.0,
-                 pitch: float = 0.0, watermark=None) -> Iterator[List[Optional[torch.Tensor]]]:
+                 pitch: float = 0.0, watermark=None, silence=None) -> Iterator[List[Optional[torch.Tensor]]]:
     """B utterances streamed in lockstep.  Yields, per step, a list of B entries: a [1, n * 1920] chunk or None.  Row b's non-None
     chunks are what ``stream(texts[b], ref=refs[b], seed=seeds[b], ...)`` yields: same chunk sizes, same stop rule (first EOS).
     ``seeds``: one per row (None: a fresh take for that row).  ``phase_locks`` = (AR lock, bulk lock): held around the AR advance and
     around refinement + decode of every step (a serving lane shares its device with whole-utterance batches).  ``timings``: seconds
     of host wall time accumulated under "ar", "refine", "decode".  ``alive(b)`` (a server): False once row b's consumer has gone - the
-    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0, ``watermark``: only None (batched streams have none of the three)."""
+    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0, ``watermark``: only None, ``silence``: only None (batched streams have none of the four)."""
     refuse_speed(speed, "stream_batch")
     refuse_pitch(pitch, "stream_batch")
     refuse_watermark(watermark, "stream_batch")
+    refuse_silence(silence, "stream_batch")
     model = tts.model
     B = len(texts)
     if B == 0 or len(refs) != B:

@@ -27,6 +27,7 @@ class PaddedBatch(NamedTuple):
     lens: List[int]        # samples
     tokens: torch.Tensor   # [B, T, Q] int64; row b is valid for frames[b] frames
     frames: Optional[List[int]] = None  # frames per row (lens[b] / 1920 unless a speaking rate stretched ``wav``)
+    cuts: Optional[List[list]] = None   # with ``silence=``: per row the (source position, samples removed) pairs (``align.map_cuts``)
 
 
 class SoproTTS:
@@ -128,7 +129,8 @@ class SoproTTS:
                    ref_tokens_tq: Optional[torch.Tensor] = None, max_frames: int = 400, top_p: float = 0.9,
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
-                   seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None) -> torch.Tensor:
+                   seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None,
+                   silence=None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
         draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed`` (new): speaking rate
@@ -138,11 +140,15 @@ class SoproTTS:
         ``speed`` makes it and every frequency - formants included - is multiplied by rho; 0.0 launches nothing.  ``speed / rho``
         must lie in [0.5, 2.0].  ``watermark`` (new): a ``sopro_amd.Watermark`` (key, tag, strength) added to the waveform as the
         last step, after rate and pitch (``hip.wm_embed``; see ``sopro_amd.watermark`` for what the mark survives); None launches
-        nothing."""
+        nothing.  ``silence`` (new): a ``sopro_amd.Silence``; pauses longer than its cap are squeezed, the silent lead-in and the tail
+        are trimmed (``hip.silence_squeeze``), after rate and pitch - its times are heard time - and before the watermark; None
+        launches nothing."""
         from . import hip
+        from .silence import check_silence
         from .watermark import check_mark
 
         check_mark(watermark)
+        check_silence(silence)
         step, inc = hip.prosody_step(speed, pitch)
         text_ids = self.encode_text(text)
         if ref is None:
@@ -157,7 +163,9 @@ class SoproTTS:
         if not hip.is_plain([(step, inc)]):
             out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
             wav = out.reshape(1, 1, -1)
-        if watermark is not None:
+        if silence is not None:
+            wav = hip.silence_squeeze(wav.reshape(1, -1), [int(wav.shape[-1])], silence)[0].reshape(1, 1, -1)
+        if watermark is not None and wav.numel() > 0:
             wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
         return wav
 
@@ -170,7 +178,7 @@ class SoproTTS:
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
                          speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
                          align_heads=None, pitch: Union[float, Sequence[float]] = 0.0,
-                         watermark=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         watermark=None, silence=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
@@ -188,14 +196,22 @@ class SoproTTS:
         ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched.
         ``watermark``: one ``sopro_amd.Watermark`` or None, or one per row with None entries allowed; the padded batch (stretched and
         shifted where asked) is marked in one launch on the bulk stream before it is sliced (``hip.wm_embed``), so ``PaddedBatch.wav``
-        is marked.  All rows None: nothing is launched, and a row at None among marked ones comes back bit for bit."""
+        is marked.  All rows None: nothing is launched, and a row at None among marked ones comes back bit for bit.
+        ``silence``: one ``sopro_amd.Silence`` or None, or one per row with None entries allowed; the padded batch (stretched and
+        shifted where asked) is squeezed in one launch sequence on the bulk stream before it is marked and sliced
+        (``hip.silence_squeeze``): ``PaddedBatch.wav`` / ``lens`` are the squeezed rows, ``cuts`` their cut tables, ``tokens`` and
+        ``frames`` stay what the model produced.  All rows None: nothing is launched, and a row at None among squeezed ones comes
+        back bit for bit."""
         import contextlib
         import time
 
         from . import hip
+        from .silence import per_row as sil_per_row
         from .watermark import per_row
 
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
+        sils = sil_per_row(silence, len(ids))
+        squeezed = any(s is not None for s in sils)
         marks = per_row(watermark, len(ids))
         marked = any(m is not None for m in marks)
         prosody = hip.prosody_steps(speed, pitch, len(ids))
@@ -280,15 +296,18 @@ class SoproTTS:
             n_samples = [n * hop for n in lens]
             if stretch:  # (rows at 1.0 / 0.0 in a mixed batch come back bit for bit: both operators are the identity there)
                 wav, n_samples = hip.apply_prosody(wav, n_samples, prosody)
+            cuts = None
+            if squeezed:  # (after rate and pitch: the cap is heard time; before the mark, which does not survive interior cuts)
+                wav, n_samples, cuts = hip.silence_squeeze(wav, n_samples, sils)
             if marked:  # (last: the mark does not survive a stretch or a resample)
                 wav = hip.wm_embed(wav, n_samples, marks)
             toks = None
             if padded:  # (the engine's own token matrix: copied before the next pass overwrites it, complete before any stream reads it)
                 toks = codes.long()
-            if padded or stretch or marked:
+            if padded or stretch or marked or squeezed:
                 self.model.bulk_stream.synchronize()
         if padded:
-            return PaddedBatch(wav, n_samples, toks, lens)
+            return PaddedBatch(wav, n_samples, toks, lens, cuts)
         return [wav[b, : n_samples[b]].reshape(1, 1, -1) for b in range(B)]
 
     @torch.inference_mode()
@@ -296,7 +315,7 @@ class SoproTTS:
                          ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
                          top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                          ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
-                         speed: float = 1.0, pitch: float = 0.0, watermark=None):
+                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None):
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
@@ -306,12 +325,15 @@ class SoproTTS:
         ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
         ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12).  ``watermark``: as
-        in ``synthesize``; the mark changes no length, so the cues do not move."""
+        in ``synthesize``; the mark changes no length, so the cues do not move.  ``silence``: as in ``synthesize``; the cues go
+        through speed, pitch and then ``align.squeeze_cues`` with the operator's own cut table (exact)."""
         from . import align as A
         from . import hip
+        from .silence import check_silence
         from .watermark import check_mark
 
         check_mark(watermark)
+        check_silence(silence)
         step, inc = hip.prosody_step(speed, pitch)
         text_ids = self.encode_text(text)
         spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
@@ -333,6 +355,10 @@ class SoproTTS:
                 words = A.stretch_cues(words, step)
             if inc != hip.PITCH_ONE:
                 words = A.shift_cues(words, inc)
+        if silence is not None and wav.numel() > 0:
+            out, _, cuts = hip.silence_squeeze(wav.reshape(1, -1), [int(wav.shape[-1])], silence)
+            wav = out.reshape(1, 1, -1)
+            words = A.squeeze_cues(words, cuts[0])
         if watermark is not None and wav.numel() > 0:
             wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
         return A.TimedResult(wav, words, sink[0])
@@ -341,41 +367,48 @@ class SoproTTS:
         """Another engine over the same device weights (own streams / scratch), for pipelining batches."""
         return SoproTTS(self.model.clone_lane(), self.cfg, self.tokenizer, self.codec.clone_lane(), str(self.device))
 
-    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[torch.Tensor]:
+    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+               **kwargs) -> Iterator[torch.Tensor]:
         """reference: src/sopro/model.py:577-580.  ``speed`` (new): speaking rate in [0.5, 2.0]; every decoded chunk goes through
         the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream).
         ``pitch`` (new): semitones in [-12, 12]; the chunks then also go through the chunked resampler and come out as [1, n].
         ``watermark`` (new): a ``sopro_amd.Watermark``; every chunk goes through a ``hip.WatermarkState`` last, so a chunk comes out
         up to 1440 samples short and the rest follows (flushed at the end).  The concatenation is ``hip.wm_embed`` of the unmarked
-        stream's concatenation, bit for bit."""
+        stream's concatenation, bit for bit.  ``silence`` (new): a ``sopro_amd.Silence``; the chunks go through a
+        ``hip.SilenceState`` after rate and pitch and before the watermark: the silent lead-in is never yielded, sound comes out at
+        once, the end of a long pause when sound resumes.  The concatenation is ``hip.silence_squeeze`` of the plain stream's
+        concatenation, bit for bit."""
         from .align import refuse_timing
         from .streaming import stream
 
         refuse_timing(kwargs, "stream")
-        return stream(self, text, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
+        return stream(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
                      nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
-                     speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
+                     speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+                     **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
         entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
         A speaking rate or a pitch is not available here (``speed`` other than 1.0 or ``pitch`` other than 0.0 raises): use
-        ``stream`` or ``synthesize_batch``.  Neither is a watermark (``watermark`` other than None raises)."""
+        ``stream`` or ``synthesize_batch``.  Neither is a watermark (``watermark`` other than None raises) or silence control
+        (``silence`` other than None raises)."""
         from .align import refuse_timing
-        from .streaming import refuse_pitch, refuse_speed, refuse_watermark, stream_batch
+        from .streaming import refuse_pitch, refuse_silence, refuse_speed, refuse_watermark, stream_batch
 
         refuse_timing(kwargs, "stream_batch")
         refuse_speed(speed, "stream_batch")
         refuse_pitch(pitch, "stream_batch")
         refuse_watermark(watermark, "stream_batch")
+        refuse_silence(silence, "stream_batch")
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
                             cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, pitch=pitch,
                             **kwargs)
 
-    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs):
+    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, **kwargs):
         """New: a text of any length (a paragraph, an article, a chapter) -> ``LongformResult``: ``wav`` [1, 1, N] on the device and
         ``segments`` [(text, start sample, end sample)] in it.  The text is cut into sentences (``longform.split_text``,
         ``max_chars``), the voice is prepared once, groups of up to ``max_rows`` segments (``plan``: "throughput", "latency" or a
@@ -389,27 +422,33 @@ class SoproTTS:
         the pauses are divided by it.  ``pitch``: semitones in [-12, 12]; every group's batch is stretched and resampled before the
         join (see ``synthesize``), the pauses are not touched by it.  ``word_cues=True`` also fills ``words`` (one ``align.LongWordCue`` per word, samples in the
         joined waveform).  ``watermark``: a ``sopro_amd.Watermark``; the batches run unmarked and the joined waveform is marked in one
-        launch, so the carrier's phase is continuous across the segments (``parts`` stay unmarked).  Full parameter list:
+        launch, so the carrier's phase is continuous across the segments (``parts`` stay unmarked).  ``silence``: a
+        ``sopro_amd.Silence``; every group's batch is squeezed before the join (``parts`` are the squeezed rows), so the pauses the
+        join puts between sentences are untouched; word cues go through ``align.squeeze_cues`` first.  Full parameter list:
         ``longform.synthesize_long``."""
         from .longform import synthesize_long
 
-        return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
+        return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
-    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, **kwargs) -> Iterator[torch.Tensor]:
+    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+                    **kwargs) -> Iterator[torch.Tensor]:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
         segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed`` and ``pitch``).
         ``watermark``: the pieces go through one ``hip.WatermarkState`` (a piece comes out up to 1440 samples short, the rest follows,
-        and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit."""
+        and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit.
+        ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
         from . import hip
         from .align import refuse_timing
         from .longform import stream_long
+        from .silence import check_silence
         from .watermark import check_mark
 
         refuse_timing(kwargs, "stream_long")
         hip.prosody_step(speed, pitch)  # (refused here, not at the first piece)
         check_mark(watermark)
-        return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, **kwargs)
+        check_silence(silence)
+        return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
     def detect_watermark(self, wav, key: int):
         """New: does ``wav`` carry the mark of ``key``?  -> ``watermark.WatermarkResult(present, score, tag, offset, z_sync, z_tag)``,

@@ -9,6 +9,7 @@
 // A row with inc == 2^32 is a copy and never touches the bank.  The chunked form keeps (next output, received, tail) per row; the
 // tiles only read it, and a second, small launch rewrites it once they are done.
 #include "common.h"
+#include "rows_window.h"
 
 namespace {
 
@@ -30,9 +31,8 @@ constexpr int PITCH_HDR = 4;
 constexpr int STATE_WORDS = PITCH_HDR + PITCH_TAIL / 2;
 
 struct Row {
-  const float* in;    // this call's samples, absolute positions [in_base, recv)
-  const float* tail;  // retained samples, absolute positions [tail_base, in_base)
-  int64_t tail_base, in_base, recv, inc;
+  RowWindow w;
+  int64_t inc;
   int64_t n0, n1;     // the outputs of this call
   bool overflow;      // they do not fit out_cap
 };
@@ -55,63 +55,19 @@ __device__ __forceinline__ Row row_setup(int row, const float* in, int64_t in_st
   n_in = recv0 + n_in > LEN_MAX ? LEN_MAX - recv0 : n_in;
   int64_t inc = incs[row];
   inc = inc < INC_MIN ? INC_MIN : (inc > INC_MAX ? INC_MAX : inc);
-  r.in = in + (int64_t)row * in_stride;
-  r.tail = hdr ? reinterpret_cast<const float*>(hdr + PITCH_HDR) : nullptr;
-  r.in_base = recv0;
-  r.tail_base = hdr ? base : recv0;
-  r.recv = recv0 + n_in;
+  r.w.in = in + (int64_t)row * in_stride;
+  r.w.tail = hdr ? reinterpret_cast<const float*>(hdr + PITCH_HDR) : nullptr;
+  r.w.in_base = recv0;
+  r.w.tail_base = hdr ? base : recv0;
+  r.w.recv = recv0 + n_in;
   r.inc = inc;
   int64_t n1;
-  if (flush) n1 = (r.recv << 32) / inc;  // M of the total length
-  else n1 = r.recv > HALF ? (((r.recv - HALF) << 32) + inc - 1) / inc : 0;  // the n with (n * inc >> 32) + 32 < recv
+  if (flush) n1 = (r.w.recv << 32) / inc;  // M of the total length
+  else n1 = r.w.recv > HALF ? (((r.w.recv - HALF) << 32) + inc - 1) / inc : 0;  // the n with (n * inc >> 32) + 32 < recv
   r.n0 = n0;
   r.n1 = n1 < n0 ? n0 : n1;
   r.overflow = r.n1 - r.n0 > out_cap;
   return r;
-}
-
-// x[i] of the row outside this call's samples: the retained tail, zero elsewhere
-__device__ __forceinline__ float row_at_tail(const Row& r, int64_t i) {
-  return (r.tail && i >= r.tail_base && i < r.in_base) ? r.tail[i - r.tail_base] : 0.0f;
-}
-
-__device__ __forceinline__ float row_at(const Row& r, int64_t i) {
-  if (i < 0 || i >= r.recv) return 0.0f;
-  return i >= r.in_base ? r.in[i - r.in_base] : row_at_tail(r, i);
-}
-
-// dst[0 .. n) = src[0 .. n) by the whole workgroup, global to LDS: 16-byte loads over the aligned body, dwords at the ragged ends
-__device__ __forceinline__ void stage_in(float* dst, const float* src, int n, int tid) {
-  int head = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(src) >> 2) & 3u)) & 3u);
-  head = head < n ? head : n;
-  const int nv = (n - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  for (int k = tid; k < head; k += PITCH_BLOCK) dst[k] = src[k];
-  const float4* sv = reinterpret_cast<const float4*>(src + head);
-  for (int v = tid; v < nv; v += PITCH_BLOCK) {
-    const float4 q = sv[v];
-    float* d = dst + head + 4 * v;
-    d[0] = q.x;
-    d[1] = q.y;
-    d[2] = q.z;
-    d[3] = q.w;
-  }
-  for (int k = tail0 + tid; k < n; k += PITCH_BLOCK) dst[k] = src[k];
-}
-
-// dst[0 .. n) = src[0 .. n), LDS to global, the same way
-__device__ __forceinline__ void store_out(float* dst, const float* src, int n, int tid) {
-  int head = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3u)) & 3u);
-  head = head < n ? head : n;
-  const int nv = (n - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  for (int k = tid; k < head; k += PITCH_BLOCK) dst[k] = src[k];
-  float4* dv = reinterpret_cast<float4*>(dst + head);
-  for (int v = tid; v < nv; v += PITCH_BLOCK) {
-    const float* s = src + head + 4 * v;
-    dv[v] = make_float4(s[0], s[1], s[2], s[3]);
-  }
-  for (int k = tail0 + tid; k < n; k += PITCH_BLOCK) dst[k] = src[k];
 }
 
 // The definition rounds every operation on its own (see tsm.hip on why this is a pragma and not a set of intrinsics).
@@ -146,13 +102,13 @@ __global__ __launch_bounds__(PITCH_BLOCK) void pitch_rows_kernel(const float* __
   }
   // [ka, kb): the part of the span that lies in this call's samples; the rest is the retained tail or zero
   const int64_t i_end = i_lo + span;
-  int64_t ga = i_lo > r.in_base ? i_lo : r.in_base, gb = i_end < r.recv ? i_end : r.recv;
+  int64_t ga = i_lo > r.w.in_base ? i_lo : r.w.in_base, gb = i_end < r.w.recv ? i_end : r.w.recv;
   ga = ga > i_end ? i_end : ga;
   gb = gb < ga ? ga : gb;
   const int ka = (int)(ga - i_lo), kb = (int)(gb - i_lo);
   for (int k = tid; k < span; k += PITCH_BLOCK)
-    if (k < ka || k >= kb) s_x[k] = row_at_tail(r, i_lo + k);
-  if (kb > ka) stage_in(s_x + ka, r.in + (ga - r.in_base), kb - ka, tid);
+    if (k < ka || k >= kb) s_x[k] = row_at_tail(r.w, i_lo + k);
+  if (kb > ka) stage_in<PITCH_BLOCK>(s_x + ka, r.w.in + (ga - r.w.in_base), kb - ka, tid);
   if (!identity) {
     int b = bank_idx[row];
     b = b < 0 ? 0 : (b >= n_banks ? n_banks - 1 : b);
@@ -194,7 +150,7 @@ __global__ __launch_bounds__(PITCH_BLOCK) void pitch_rows_kernel(const float* __
     s_y[m] = acc;
   }
   __syncthreads();
-  store_out(out + (int64_t)row * out_stride + (na - r.n0), s_y, cnt, tid);  // (na - n0 + cnt <= n1 - n0 <= out_cap)
+  store_out<PITCH_BLOCK>(out + (int64_t)row * out_stride + (na - r.n0), s_y, cnt, tid);  // (na - n0 + cnt <= n1 - n0 <= out_cap)
 }
 
 // The end of a chunked call: one workgroup per row rewrites the row's state once every tile of the call has read it (stream order).
@@ -214,16 +170,16 @@ __global__ __launch_bounds__(STATE_BLOCK) void pitch_state_kernel(const float* _
   }
   // what the next output may read: everything from i_next - 31 on (never before the current base, never past what was received)
   int64_t nb = (int64_t)(((uint64_t)r.n1 * (uint64_t)r.inc) >> 32) - (HALF - 1);
-  nb = nb < r.tail_base ? r.tail_base : nb;
-  nb = nb > r.recv ? r.recv : nb;
-  if (r.recv - nb > PITCH_TAIL) nb = r.recv - PITCH_TAIL;  // (unreachable: the bound in sopro_hip.h)
-  const int keep = (int)(r.recv - nb);
-  for (int k = tid; k < keep; k += STATE_BLOCK) s_keep[k] = row_at(r, nb + k);
+  nb = nb < r.w.tail_base ? r.w.tail_base : nb;
+  nb = nb > r.w.recv ? r.w.recv : nb;
+  if (r.w.recv - nb > PITCH_TAIL) nb = r.w.recv - PITCH_TAIL;  // (unreachable: the bound in sopro_hip.h)
+  const int keep = (int)(r.w.recv - nb);
+  for (int k = tid; k < keep; k += STATE_BLOCK) s_keep[k] = row_at(r.w, nb + k);
   __syncthreads();  // the old tail has been read
   for (int k = tid; k < keep; k += STATE_BLOCK) tail[k] = s_keep[k];
   if (tid == 0) {
     hdr[H_N] = r.n1;
-    hdr[H_RECV] = r.recv;
+    hdr[H_RECV] = r.w.recv;
     hdr[H_BASE] = nb;
   }
 }

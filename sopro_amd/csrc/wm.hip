@@ -15,6 +15,7 @@
 // templates in LDS; a lane owns four offsets 256 apart, so the lanes of a wave read consecutive words of f and every template word is
 // a broadcast shared by eight accumulators.  peak: one workgroup per (lane, row), float64 moments.
 #include "common.h"
+#include "rows_window.h"
 
 namespace {
 
@@ -36,9 +37,7 @@ constexpr int WM_HDR = 4;
 constexpr int STATE_WORDS = WM_HDR + WM_TAIL / 2;
 
 struct Row {
-  const float* in;    // this call's samples, absolute positions [in_base, recv)
-  const float* tail;  // retained samples, absolute positions [tail_base, in_base)
-  int64_t tail_base, in_base, recv;
+  RowWindow w;
   int64_t n0, n1;     // the samples this call emits
   bool overflow;      // they do not fit out_cap
 };
@@ -59,60 +58,16 @@ __device__ __forceinline__ Row row_setup(int row, const float* in, int64_t in_st
   int64_t n_in = in_lens[row];
   n_in = n_in < 0 ? 0 : (n_in > in_cap ? in_cap : n_in);
   n_in = recv0 + n_in > LEN_MAX ? LEN_MAX - recv0 : n_in;
-  r.in = in + (int64_t)row * in_stride;
-  r.tail = hdr ? reinterpret_cast<const float*>(hdr + WM_HDR) : nullptr;
-  r.in_base = recv0;
-  r.tail_base = hdr ? base : recv0;
-  r.recv = recv0 + n_in;
-  const int64_t n1 = flush ? r.recv : (r.recv / HS - 1) * HS;  // block k is ready once recv >= (k + 2) HS
+  r.w.in = in + (int64_t)row * in_stride;
+  r.w.tail = hdr ? reinterpret_cast<const float*>(hdr + WM_HDR) : nullptr;
+  r.w.in_base = recv0;
+  r.w.tail_base = hdr ? base : recv0;
+  r.w.recv = recv0 + n_in;
+  const int64_t n1 = flush ? r.w.recv : (r.w.recv / HS - 1) * HS;  // block k is ready once recv >= (k + 2) HS
   r.n0 = n0;
   r.n1 = n1 < n0 ? n0 : n1;
   r.overflow = r.n1 - r.n0 > out_cap;
   return r;
-}
-
-// x[i] of the row outside this call's samples: the retained tail, zero elsewhere
-__device__ __forceinline__ float row_at_tail(const Row& r, int64_t i) {
-  return (r.tail && i >= r.tail_base && i < r.in_base) ? r.tail[i - r.tail_base] : 0.0f;
-}
-
-__device__ __forceinline__ float row_at(const Row& r, int64_t i) {
-  if (i < 0 || i >= r.recv) return 0.0f;
-  return i >= r.in_base ? r.in[i - r.in_base] : row_at_tail(r, i);
-}
-
-// dst[0 .. n) = src[0 .. n) by the whole workgroup, global to LDS: 16-byte loads over the aligned body, dwords at the ragged ends
-__device__ __forceinline__ void stage_in(float* dst, const float* src, int n, int tid) {
-  int head = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(src) >> 2) & 3u)) & 3u);
-  head = head < n ? head : n;
-  const int nv = (n - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  for (int k = tid; k < head; k += WM_BLOCK) dst[k] = src[k];
-  const float4* sv = reinterpret_cast<const float4*>(src + head);
-  for (int v = tid; v < nv; v += WM_BLOCK) {
-    const float4 q = sv[v];
-    float* d = dst + head + 4 * v;
-    d[0] = q.x;
-    d[1] = q.y;
-    d[2] = q.z;
-    d[3] = q.w;
-  }
-  for (int k = tail0 + tid; k < n; k += WM_BLOCK) dst[k] = src[k];
-}
-
-// dst[0 .. n) = src[0 .. n), LDS to global, the same way
-__device__ __forceinline__ void store_out(float* dst, const float* src, int n, int tid) {
-  int head = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3u)) & 3u);
-  head = head < n ? head : n;
-  const int nv = (n - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  for (int k = tid; k < head; k += WM_BLOCK) dst[k] = src[k];
-  float4* dv = reinterpret_cast<float4*>(dst + head);
-  for (int v = tid; v < nv; v += WM_BLOCK) {
-    const float* s = src + head + 4 * v;
-    dv[v] = make_float4(s[0], s[1], s[2], s[3]);
-  }
-  for (int k = tail0 + tid; k < n; k += WM_BLOCK) dst[k] = src[k];
 }
 
 // The definition rounds every operation on its own (see tsm.hip on why this is a pragma and not a set of intrinsics).
@@ -143,13 +98,13 @@ __global__ __launch_bounds__(WM_BLOCK) void wm_embed_kernel(const float* __restr
   const int64_t i_lo = na - HS;
   const int k_lo = marked ? 0 : HS, k_hi = marked ? SPAN : HS + cnt;
   // [ka, kb): the part of it that lies in this call's samples; the rest is the retained tail or zero
-  int64_t ga = i_lo + k_lo > r.in_base ? i_lo + k_lo : r.in_base, gb = i_lo + k_hi < r.recv ? i_lo + k_hi : r.recv;
+  int64_t ga = i_lo + k_lo > r.w.in_base ? i_lo + k_lo : r.w.in_base, gb = i_lo + k_hi < r.w.recv ? i_lo + k_hi : r.w.recv;
   ga = ga > i_lo + k_hi ? i_lo + k_hi : ga;
   gb = gb < ga ? ga : gb;
   const int ka = (int)(ga - i_lo), kb = (int)(gb - i_lo);
   for (int k = k_lo + tid; k < k_hi; k += WM_BLOCK)
-    if (k < ka || k >= kb) s_x[k] = row_at_tail(r, i_lo + k);
-  if (kb > ka) stage_in(s_x + ka, r.in + (ga - r.in_base), kb - ka, tid);
+    if (k < ka || k >= kb) s_x[k] = row_at_tail(r.w, i_lo + k);
+  if (kb > ka) stage_in<WM_BLOCK>(s_x + ka, r.w.in + (ga - r.w.in_base), kb - ka, tid);
   if (marked)
     for (int k = tid; k < HS; k += WM_BLOCK) s_tab[k] = tab[k];
   __syncthreads();
@@ -188,7 +143,7 @@ __global__ __launch_bounds__(WM_BLOCK) void wm_embed_kernel(const float* __restr
     }
     __syncthreads();
   }
-  store_out(out + (int64_t)row * out_stride + (na - r.n0), s_x + HS, cnt, tid);  // (na - n0 + cnt <= n1 - n0 <= out_cap)
+  store_out<WM_BLOCK>(out + (int64_t)row * out_stride + (na - r.n0), s_x + HS, cnt, tid);  // (na - n0 + cnt <= n1 - n0 <= out_cap)
 }
 
 // The end of a chunked call: one workgroup per row rewrites the row's state once every tile of the call has read it (stream order).
@@ -207,16 +162,16 @@ __global__ __launch_bounds__(STATE_BLOCK) void wm_state_kernel(const float* __re
   }
   // what the next block may read: everything from (k_next - 1) HS on (never before the current base, never past what was received)
   int64_t nb = r.n1 - HS;
-  nb = nb < r.tail_base ? r.tail_base : nb;
-  nb = nb > r.recv ? r.recv : nb;
-  if (r.recv - nb > WM_TAIL) nb = r.recv - WM_TAIL;  // (unreachable: the bound in sopro_hip.h)
-  const int keep = (int)(r.recv - nb);
-  for (int k = tid; k < keep; k += STATE_BLOCK) s_keep[k] = row_at(r, nb + k);
+  nb = nb < r.w.tail_base ? r.w.tail_base : nb;
+  nb = nb > r.w.recv ? r.w.recv : nb;
+  if (r.w.recv - nb > WM_TAIL) nb = r.w.recv - WM_TAIL;  // (unreachable: the bound in sopro_hip.h)
+  const int keep = (int)(r.w.recv - nb);
+  for (int k = tid; k < keep; k += STATE_BLOCK) s_keep[k] = row_at(r.w, nb + k);
   __syncthreads();  // the old tail has been read
   for (int k = tid; k < keep; k += STATE_BLOCK) tail[k] = s_keep[k];
   if (tid == 0) {
     hdr[H_N] = r.n1;
-    hdr[H_RECV] = r.recv;
+    hdr[H_RECV] = r.w.recv;
     hdr[H_BASE] = nb;
   }
 }

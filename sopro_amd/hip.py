@@ -990,6 +990,11 @@ def fade_table(fade_len: int, device) -> Optional[torch.Tensor]:
     return t
 
 
+def _lens_list(lens) -> List[int]:
+    """Per-row integers (lengths, gaps) as a host list, from a host sequence or a tensor."""
+    return [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+
+
 def join_segments(wav: torch.Tensor, lens, gaps, *, hop: int = 240, rel: float = 0.01, keep: int = 3, fade_len: int = 120,
                   trim: bool = True, out: Optional[torch.Tensor] = None):
     """The long-form join (sopro_join_edges_f32 / _layout_i64 / _mix_f32, contract in include/sopro_hip.h): ``wav`` fp32
@@ -997,8 +1002,8 @@ def join_segments(wav: torch.Tensor, lens, gaps, *, hop: int = 240, rel: float =
     ``gaps`` samples of silence after each row (host sequences) -> (out[:total] on the device, edges int32 [n_seg, 2] and offs int64
     [n_seg + 1] on the host).  ``out`` is allocated at the upper bound sum(lens) + sum(gaps) unless given; the three steps are
     launched back to back on the current stream and the one host copy of (offs | edges) at the end is the only synchronisation."""
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-    gaps_h = [int(v) for v in (gaps.tolist() if isinstance(gaps, torch.Tensor) else gaps)]
+    lens_h = _lens_list(lens)
+    gaps_h = _lens_list(gaps)
     n = len(lens_h)
     ptr(wav)  # a contiguous-row fp32 tensor on the device, or it raises here
     if wav.dim() != 2 or int(wav.shape[0]) != n or len(gaps_h) != n:
@@ -1056,12 +1061,7 @@ def tsm_step(speed) -> int:
 
 def tsm_steps(speed, rows: int) -> List[int]:
     """One step per row from a float or one float per row."""
-    if isinstance(speed, (list, tuple)) or (hasattr(speed, "__len__") and not isinstance(speed, str)):
-        vals = [tsm_step(v) for v in speed]
-        if len(vals) != int(rows):
-            raise ValueError(f"speed: one value or one per row ({rows}), got {len(vals)}")
-        return vals
-    return [tsm_step(speed)] * int(rows)
+    return [tsm_step(v) for v in _per_row(speed, rows, "speed")]
 
 
 def tsm_out_len(in_len: int, step: int) -> int:
@@ -1096,7 +1096,7 @@ def _tsm_launch(wav, in_cap: int, lens_h, steps_h, state, flush: bool, out, want
     return out_lens, deltas, blocks_cap
 
 
-def _tsm_check_rows(wav: torch.Tensor, lens_h: List[int], what: str) -> None:
+def _check_rows(wav: torch.Tensor, lens_h: List[int], what: str) -> None:
     ptr(wav)
     if wav.dim() != 2 or int(wav.shape[0]) != len(lens_h):
         raise SoproHipError(f"{what} wants wav [rows, samples] with one length per row, got {tuple(wav.shape)} and {len(lens_h)} lengths")
@@ -1104,6 +1104,45 @@ def _tsm_check_rows(wav: torch.Tensor, lens_h: List[int], what: str) -> None:
         raise SoproHipError(f"{what}: lens must lie in [0, wav.shape[1]]")
     if int(wav.shape[1]) > 1 and wav.stride(1) != 1:
         raise SoproHipError(f"{what}: the samples of a row must be contiguous")
+
+
+def _out_buffer(out: Optional[torch.Tensor], rows: int, cap: int, what: str) -> None:
+    """A caller's ``out=`` holds fp32 [rows, >= cap] with contiguous rows (None: the operator allocates its own)."""
+    if out is None:
+        return
+    ptr(out)
+    if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
+        raise SoproHipError(f"{what}: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+
+
+class _RowsState:
+    """What the chunked forms share: ``rows`` streams whose state lives on the device (``sopro_<op>_state_bytes``), the chunk a
+    ``feed`` takes with the buffer its output goes to (``sopro_<op>_chunk_out_cap``), and ``flush``."""
+    _op = ""  # tsm, pitch, wm, sil
+
+    def __init__(self, rows: int, device):
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError("rows >= 1")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise SoproHipError(f"{type(self).__name__} lives on a HIP device: the Sopro hot path has no CPU fallback")
+        self.state = torch.zeros(int(getattr(load(), f"sopro_{self._op}_state_bytes")(self.rows)) // 8, dtype=torch.int64, device=self.device)
+
+    def _chunk(self, wav: Optional[torch.Tensor], lens):
+        """``wav`` [rows, n] or None, ``lens`` valid samples per row (default n) -> (n, lens on the host, the call's output buffer)."""
+        if wav is None:
+            n, lens_h = 0, [0] * self.rows
+        else:
+            n = int(wav.shape[-1])
+            lens_h = [n] * self.rows if lens is None else _lens_list(lens)
+            _check_rows(wav, lens_h, f"{type(self).__name__}.feed")
+        cap = int(getattr(load(), f"sopro_{self._op}_chunk_out_cap")(n))
+        return n, lens_h, torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+
+    def flush(self):
+        """What the rows still hold back, their input taken as ended; the state is fresh afterwards."""
+        return self.feed(None, flush=True)
 
 
 def _tsm_steps_given(steps, rows: int) -> List[int]:
@@ -1122,18 +1161,15 @@ def time_stretch(wav: torch.Tensor, lens, speed, *, out: Optional[torch.Tensor] 
     [rows, >= max(out_lens)] fp32 buffer to write into (nothing past a row's out_len is touched).  ``deltas=True`` (tests,
     debugging) also returns the chosen offsets d_k per row as lists, and checks the lengths the device reports (one host copy).
     ``steps``: one step per row instead of ``speed`` (which is then not looked at)."""
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    lens_h = _lens_list(lens)
     rows = len(lens_h)
-    _tsm_check_rows(wav, lens_h, "time_stretch")
+    _check_rows(wav, lens_h, "time_stretch")
     steps_h = tsm_steps(speed, rows) if steps is None else _tsm_steps_given(steps, rows)
     out_lens_h = [tsm_out_len(n, s) for n, s in zip(lens_h, steps_h)]
     cap = max(out_lens_h, default=0)
+    _out_buffer(out, rows, cap, "time_stretch")
     if out is None:
         out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=wav.device)
-    else:
-        ptr(out)
-        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
-            raise SoproHipError(f"time_stretch: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
     if rows == 0:
         return (out[:, :0], [], []) if deltas else (out[:, :0], [])
     got_d, deltas_d, blocks_cap = _tsm_launch(wav, int(wav.shape[1]), lens_h, steps_h, None, True, out, deltas)
@@ -1147,32 +1183,21 @@ def time_stretch(wav: torch.Tensor, lens, speed, *, out: Optional[torch.Tensor] 
     return res, out_lens_h, [d[b][: tsm_blocks(out_lens_h[b])] for b in range(rows)]
 
 
-class TimeStretchState:
+class TimeStretchState(_RowsState):
     """Chunked form of ``time_stretch`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the blocks that became
     ready, ``flush`` the rest.  Any chunking followed by ``flush`` gives the one-shot result bit for bit.  The state (block index,
     last position, samples received, a retained tail of < 1920 samples per row) lives on the device; every call is one launch and
     one small host copy (the lengths it produced)."""
 
+    _op = "tsm"
+
     def __init__(self, rows: int, speed, device, *, steps=None):
-        self.rows = int(rows)
-        if self.rows < 1:
-            raise ValueError("rows >= 1")
+        super().__init__(rows, device)
         self.steps = tsm_steps(speed, self.rows) if steps is None else _tsm_steps_given(steps, self.rows)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise SoproHipError("TimeStretchState lives on a HIP device: the Sopro hot path has no CPU fallback")
-        self.state = torch.zeros(int(load().sopro_tsm_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
 
     def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False, deltas: bool = False):
         """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens[, deltas])."""
-        if wav is None:
-            n, lens_h = 0, [0] * self.rows
-        else:
-            n = int(wav.shape[-1])
-            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-            _tsm_check_rows(wav, lens_h, "TimeStretchState.feed")
-        cap = int(load().sopro_tsm_chunk_out_cap(n))
-        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        n, lens_h, out = self._chunk(wav, lens)
         got_d, deltas_d, _ = _tsm_launch(wav, n, lens_h, self.steps, self.state, flush, out, deltas)
         got = got_d.tolist()
         if min(got) < 0:
@@ -1326,20 +1351,17 @@ def pitch_shift(wav: torch.Tensor, lens, pitch, *, out: Optional[torch.Tensor] =
     (the public ``pitch=`` stretches by the same ratio first: ``prosody_steps``).  One launch on the current stream and no
     synchronisation: the output lengths are host arithmetic.  ``out``: a [rows, >= max(out_lens)] fp32 buffer to write into
     (nothing past a row's out_len is touched).  ``incs``: one increment per row instead of ``pitch``."""
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    lens_h = _lens_list(lens)
     rows = len(lens_h)
-    _tsm_check_rows(wav, lens_h, "pitch_shift")
+    _check_rows(wav, lens_h, "pitch_shift")
     incs_h = pitch_incs(pitch, rows) if incs is None else [int(v) for v in incs]
     if len(incs_h) != rows:
         raise ValueError(f"incs: one per row ({rows}), got {len(incs_h)}")
     out_lens_h = [pitch_out_len(n, s) for n, s in zip(lens_h, incs_h)]
     cap = max(out_lens_h, default=0)
+    _out_buffer(out, rows, cap, "pitch_shift")
     if out is None:
         out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=wav.device)
-    else:
-        ptr(out)
-        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
-            raise SoproHipError(f"pitch_shift: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
     if rows == 0:
         return out[:, :0], []
     _pitch_launch(wav, int(wav.shape[1]), lens_h, incs_h, None, True, out)
@@ -1350,7 +1372,7 @@ def apply_prosody(wav: torch.Tensor, lens, pairs) -> Tuple[torch.Tensor, List[in
     """Speaking rate and pitch on a padded batch: ``time_stretch`` at every row's step', then ``pitch_shift`` at its inc
     (``pairs`` from ``prosody_steps``), on the current stream.  A stage at its identity for every row is not launched; a row at
     its identity in a launched stage comes back bit for bit."""
-    lens = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    lens = _lens_list(lens)
     steps, incs = [p[0] for p in pairs], [p[1] for p in pairs]
     if any(s != TSM_HS << 16 for s in steps):
         wav, lens = time_stretch(wav, lens, None, steps=steps)
@@ -1359,42 +1381,27 @@ def apply_prosody(wav: torch.Tensor, lens, pairs) -> Tuple[torch.Tensor, List[in
     return wav, lens
 
 
-class PitchShiftState:
+class PitchShiftState(_RowsState):
     """Chunked form of ``pitch_shift`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the outputs whose taps
     are all in, ``flush`` the rest.  Any chunking followed by ``flush`` gives the one-shot result bit for bit.  The state (next
     output, samples received, a retained tail of < 64 samples per row) lives on the device; every call is one launch plus the
     state's small update and one small host copy (the lengths it produced)."""
 
+    _op = "pitch"
+
     def __init__(self, rows: int, pitch, device, *, incs=None):
-        self.rows = int(rows)
-        if self.rows < 1:
-            raise ValueError("rows >= 1")
+        super().__init__(rows, device)
         self.incs = pitch_incs(pitch, self.rows) if incs is None else [int(v) for v in incs]
         if len(self.incs) != self.rows:
             raise ValueError(f"incs: one per row ({self.rows}), got {len(self.incs)}")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise SoproHipError("PitchShiftState lives on a HIP device: the Sopro hot path has no CPU fallback")
-        self.state = torch.zeros(int(load().sopro_pitch_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
 
     def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False):
         """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
-        if wav is None:
-            n, lens_h = 0, [0] * self.rows
-        else:
-            n = int(wav.shape[-1])
-            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-            _tsm_check_rows(wav, lens_h, "PitchShiftState.feed")
-        cap = int(load().sopro_pitch_chunk_out_cap(n))
-        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        n, lens_h, out = self._chunk(wav, lens)
         got = _pitch_launch(wav, n, lens_h, self.incs, self.state, flush, out).tolist()
         if min(got) < 0:
             raise SoproHipError("PitchShiftState: a row's outputs did not fit the output buffer")
         return out[:, : max(got)], got
-
-    def flush(self):
-        """The remaining outputs (zero extension, up to the row's total output length); the state is fresh afterwards."""
-        return self.feed(None, flush=True)
 
 
 # ---- watermark (sopro_wm_*; definition in include/sopro_hip.h, numpy restatement in tests/wm_ref.py; host tables in watermark.py) ----
@@ -1440,15 +1447,12 @@ def wm_embed(wav: torch.Tensor, lens, marks, *, out: Optional[torch.Tensor] = No
     returned as it is."""
     from . import watermark as wm
 
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    lens_h = _lens_list(lens)
     rows = len(lens_h)
-    _tsm_check_rows(wav, lens_h, "wm_embed")
+    _check_rows(wav, lens_h, "wm_embed")
     marks = wm.per_row(marks, rows, "marks")
     cap = max(lens_h, default=0)
-    if out is not None:
-        ptr(out)
-        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
-            raise SoproHipError(f"wm_embed: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+    _out_buffer(out, rows, cap, "wm_embed")
     if rows == 0 or all(m is None for m in marks):
         if out is None:
             return wav[:, :cap]
@@ -1460,43 +1464,28 @@ def wm_embed(wav: torch.Tensor, lens, marks, *, out: Optional[torch.Tensor] = No
     return out[:, :cap]
 
 
-class WatermarkState:
+class WatermarkState(_RowsState):
     """Chunked form of ``wm_embed`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the 480-sample blocks whose
     envelope is final (a chunk comes out up to 1440 samples short, and the rest follows), ``flush`` the rest.  Any chunking followed
     by ``flush`` gives the one-shot result bit for bit.  The state (samples emitted, samples received, a retained tail of < 1440
     samples per row) lives on the device; every call is one launch plus the state's small update and one small host copy (the
     lengths it produced)."""
 
+    _op = "wm"
+
     def __init__(self, rows: int, marks, device):
         from . import watermark as wm
 
-        self.rows = int(rows)
-        if self.rows < 1:
-            raise ValueError("rows >= 1")
+        super().__init__(rows, device)
         self.marks = wm.per_row(marks, self.rows, "marks")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise SoproHipError("WatermarkState lives on a HIP device: the Sopro hot path has no CPU fallback")
-        self.state = torch.zeros(int(load().sopro_wm_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
 
     def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False):
         """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
-        if wav is None:
-            n, lens_h = 0, [0] * self.rows
-        else:
-            n = int(wav.shape[-1])
-            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-            _tsm_check_rows(wav, lens_h, "WatermarkState.feed")
-        cap = int(load().sopro_wm_chunk_out_cap(n))
-        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
+        n, lens_h, out = self._chunk(wav, lens)
         got = _wm_launch(wav, n, lens_h, self.marks, self.state, flush, out).tolist()
         if min(got) < 0:
             raise SoproHipError("WatermarkState: a row's samples did not fit the output buffer")
         return out[:, : max(got)], got
-
-    def flush(self):
-        """The remaining samples (zero extension of the envelope); the state is fresh afterwards."""
-        return self.feed(None, flush=True)
 
 
 def wm_detect_rows(wav: torch.Tensor, lens, keys, *, details: bool = False):
@@ -1506,9 +1495,9 @@ def wm_detect_rows(wav: torch.Tensor, lens, keys, *, details: bool = False):
     statistics per row).  ``details=True`` (tests) also returns the folded rows f [rows, 8192] and the correlations R [rows, 2, 8192]."""
     from . import watermark as wm
 
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    lens_h = _lens_list(lens)
     rows = len(lens_h)
-    _tsm_check_rows(wav, lens_h, "wm_detect_rows")
+    _check_rows(wav, lens_h, "wm_detect_rows")
     keys = list(keys)
     if len(keys) != rows:
         raise ValueError(f"keys: one per row ({rows}), got {len(keys)}")
@@ -1589,15 +1578,12 @@ def silence_squeeze(wav: torch.Tensor, lens, sils, *, out: Optional[torch.Tensor
     buffer to write into; it must not overlap ``wav``.  All None: nothing is launched and ``wav[:, :max(lens)]`` is returned as it is."""
     from . import silence as S
 
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    lens_h = _lens_list(lens)
     rows = len(lens_h)
-    _tsm_check_rows(wav, lens_h, "silence_squeeze")
+    _check_rows(wav, lens_h, "silence_squeeze")
     sils = S.per_row(sils, rows, "sils")
     cap = max(lens_h, default=0)
-    if out is not None:
-        ptr(out)
-        if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < cap or (int(out.shape[1]) > 1 and out.stride(1) != 1):
-            raise SoproHipError(f"silence_squeeze: out must be fp32 [rows, >= {cap}] with contiguous rows, got {tuple(out.shape)}")
+    _out_buffer(out, rows, cap, "silence_squeeze")
     if rows == 0 or all(s is None for s in sils):
         if out is None:
             return wav[:, :cap], lens_h, [[] for _ in range(rows)]
@@ -1611,24 +1597,20 @@ def silence_squeeze(wav: torch.Tensor, lens, sils, *, out: Optional[torch.Tensor
     return out[:, : max(got)], got, cuts
 
 
-class SilenceState:
+class SilenceState(_RowsState):
     """Chunked form of ``silence_squeeze`` for ``rows`` streams: ``feed`` appends a chunk per row and returns what is decided (sound
     at once, the first hops of a pause at once, the rest of a pause when sound resumes), ``flush`` the rest.  Any chunking followed by
     ``flush`` gives the one-shot result bit for bit.  The state (speech seen, run length, samples received and emitted, a retained
     tail of at most 18 hops and 239 samples per row) lives on the device; every call is four launches and one small host copy.
     ``cuts[b]`` collects row b's cuts, in the row's total source coordinates, until the flush that ends the row."""
 
+    _op = "sil"
+
     def __init__(self, rows: int, sils, device):
         from . import silence as S
 
-        self.rows = int(rows)
-        if self.rows < 1:
-            raise ValueError("rows >= 1")
+        super().__init__(rows, device)
         self.sils = S.per_row(sils, self.rows, "sils")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise SoproHipError("SilenceState lives on a HIP device: the Sopro hot path has no CPU fallback")
-        self.state = torch.zeros(int(load().sopro_sil_state_bytes(self.rows)) // 8, dtype=torch.int64, device=self.device)
         self.recv = [0] * self.rows
         self.cuts: List[list] = [[] for _ in range(self.rows)]
         self._ended = False
@@ -1637,15 +1619,8 @@ class SilenceState:
         """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
         if self._ended:  # (the first call after a flush starts new rows)
             self.recv, self.cuts, self._ended = [0] * self.rows, [[] for _ in range(self.rows)], False
-        if wav is None:
-            n, lens_h = 0, [0] * self.rows
-        else:
-            n = int(wav.shape[-1])
-            lens_h = [n] * self.rows if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-            _tsm_check_rows(wav, lens_h, "SilenceState.feed")
+        n, lens_h, out = self._chunk(wav, lens)
         self.recv = [a + b for a, b in zip(self.recv, lens_h)]
-        cap = int(load().sopro_sil_chunk_out_cap(n))
-        out = torch.empty(self.rows, cap, dtype=torch.float32, device=self.device)
         got, cuts = _sil_launch(wav, n, lens_h, self.recv, self.sils, self.state, flush, out)
         if min(got) < 0:
             raise SoproHipError("SilenceState: a row's samples or cuts did not fit")
@@ -1653,10 +1628,6 @@ class SilenceState:
             self.cuts[b] += cuts[b]
         self._ended = bool(flush)
         return out[:, : max(got)], got
-
-    def flush(self):
-        """The remaining samples (the partial last hop and the trailing run are decided); the state is fresh afterwards."""
-        return self.feed(None, flush=True)
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

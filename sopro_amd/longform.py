@@ -182,26 +182,26 @@ class _Group(NamedTuple):
 
 
 def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top_p, temperature, anti_loop, style_strength, min_gen_frames,
-            seed, pauses_ms, join_kw, speed=1.0, word_cues=False, align_heads=None, pitch=0.0, silence=None) -> Iterator[_Group]:
+            seed, pauses_ms, join_kw, fx, word_cues=False, align_heads=None) -> Iterator[_Group]:
     """Run the groups in order: one ``synthesize_batch`` and one ``hip.join_segments`` each, straight from the decoder's padded
     batch.  Segment k of the text draws with nonce (seed + k) & 0xFFFFFFFF and row id 0 - the sampler stream
-    ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce.  ``speed``: the
-    batch comes back stretched (rows in parallel, before the join: trimming, fades and cue times then refer to the audio as it is
-    heard) and the pauses shrink or grow with it.  ``pitch``: the batch comes back shifted as well; the pauses follow ``speed`` only.
-    ``silence``: the batch comes back squeezed (``batch.cuts``); the operator never sees the pauses the join adds."""
+    ``synthesize(segment_k, ref=ref, seed=seed + k)`` uses; without a seed every segment takes a fresh nonce.  ``fx``: every row's
+    ``effects.Effects``; the batch comes back with them applied (rows in parallel, before the join: trimming, fades and cue times then
+    refer to the audio as it is heard, and the squeeze never sees the pauses the join adds) and the pauses shrink or grow with
+    ``fx.speed`` only."""
     from . import hip
 
     n = len(segs)
     nonces = [(int(seed) + k) & 0xFFFFFFFF if seed is not None else tts.model.next_nonce(None) for k in range(n)]
-    gaps = [scaled_pause(pause_samples(s.boundary, pauses_ms), speed) for s in segs]
+    gaps = [scaled_pause(pause_samples(s.boundary, pauses_ms), fx.speed) for s in segs]
     gaps[-1] = 0  # nothing follows the last segment
     k0 = 0
     for g in groups:
         sink = [] if word_cues else None  # (None: the pass launches nothing for timing)
         batch = tts.synthesize_batch([s.text for s in segs[k0: k0 + g]], [ref] * g, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                      anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed,
-                                     nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, speed=speed, alignment=sink,
-                                     align_heads=align_heads, pitch=pitch, silence=silence)
+                                     nonces=nonces[k0: k0 + g], row_ids=[0] * g, padded=True, alignment=sink,
+                                     align_heads=align_heads, effects=[fx] * g)
         piece, edges, offs = hip.join_segments(batch.wav, batch.lens, gaps[k0: k0 + g], **join_kw)
         yield _Group(k0, piece, edges, offs, batch, sink)
         k0 += g
@@ -224,23 +224,20 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     pitch: float = 0.0, watermark=None, silence=None) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
-    (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k; at a ``speed`` other than 1.0 the
-    cue goes through ``align.map_speed`` first, at a ``pitch`` other than 0.0 through ``align.stretch_cues`` at the stretch's own step
-    and ``align.shift_cues``).  ``token_spans``: a callable text -> [(start, end)] per token id for tokenizers
-    that give no character offsets; ``align_heads``: the (layer, head) pairs to average.  ``watermark``: the batches get no mark;
-    the joined waveform is marked in one launch (``hip.wm_embed``), so the carrier's phase runs on across the segments and no cue
-    moves.  ``silence``: a ``sopro_amd.Silence``; every group's batch is squeezed before the join, so the join's own sentence gaps
-    are untouched, and a word cue goes through ``align.squeeze_cues`` with its row's cut table before ``align.long_cue``."""
+    (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k, after ``effects.map_cues`` has
+    taken it through its row's rate, pitch and cut table).  ``token_spans``: a callable text -> [(start, end)] per token id for
+    tokenizers that give no character offsets; ``align_heads``: the (layer, head) pairs to average.  ``watermark``: the batches get no
+    mark (parts stay unmarked); the joined waveform is marked in one launch, so the carrier's phase runs on across the segments and no
+    cue moves."""
+    import dataclasses
+
     import torch
 
     from . import align as A
-    from . import hip
-    from .silence import check_silence
-    from .watermark import check_mark
+    from . import effects
 
-    step, inc = hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused before anything runs)
-    check_mark(watermark)
-    check_silence(silence)
+    fx = effects.Effects.of(speed, pitch, silence, watermark)  # (a bad value is refused before anything runs)
+    rows = dataclasses.replace(fx, watermark=None)
     if token_spans is not None and not callable(token_spans):
         raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
     spans_of = token_spans if token_spans is not None else (lambda t: A.token_spans(tts.tokenizer, t))
@@ -254,8 +251,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     words = [] if word_cues else None
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, word_cues=word_cues, align_heads=align_heads,
-                       pitch=pitch, silence=silence):
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), fx=rows, word_cues=word_cues, align_heads=align_heads):
         pieces.append(grp.piece)
         offs, edges = grp.offs.tolist(), grp.edges.tolist()
         for i, (s, e) in enumerate(edges):
@@ -263,12 +259,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
             if word_cues:
                 seg_text = segs[grp.first + i].text
                 wc = A.word_cues(seg_text, spans_of(seg_text), grp.align[i].token_frames)
-                if step != hip.TSM_HS << 16:
-                    wc = A.stretch_cues(wc, step)
-                if inc != hip.PITCH_ONE:
-                    wc = A.shift_cues(wc, inc)
-                if grp.batch.cuts is not None:
-                    wc = A.squeeze_cues(wc, grp.batch.cuts[i])
+                wc = effects.map_cues(wc, rows, grp.batch.cuts[i] if grp.batch.cuts is not None else None)
                 words.extend(A.long_cue(c, grp.first + i, base + offs[i], s, e) for c in wc)
             if keep_parts:
                 n = grp.batch.lens[i]
@@ -276,8 +267,8 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                 all_edges.append((s, e))
         base += offs[-1]
     wav = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).reshape(1, 1, -1)
-    if watermark is not None and wav.numel() > 0:
-        wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
+    if fx.watermark is not None:
+        wav = effects.apply(wav.reshape(1, -1), [int(wav.shape[-1])], [effects.Effects(watermark=fx.watermark)])[0].reshape(1, 1, -1)
     return LongformResult(wav, cues, groups, parts if keep_parts else None, all_edges if keep_parts else None, words)
 
 
@@ -288,30 +279,23 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0,
                 pitch: float = 0.0, watermark=None, silence=None) -> Iterator[Any]:
     """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``).
-    ``watermark``: every piece goes through one ``hip.WatermarkState`` (what is ready of it is yielded, nothing when that is empty)
+    ``watermark``: every piece goes through one mark-only ``effects.Chain`` (what is ready of it is yielded, nothing when that is empty)
     and a last piece carries the flush.  ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
-    from . import hip
-    from .silence import check_silence
-    from .watermark import check_mark
+    import dataclasses
 
-    hip.prosody_step(speed, pitch)
-    check_mark(watermark)
-    check_silence(silence)
+    from .effects import Chain, Effects
+
+    fx = Effects.of(speed, pitch, silence, watermark)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows)
     if not segs:
         return
-    wms = hip.WatermarkState(1, watermark, tts.device) if watermark is not None else None
+    mark = Chain.of(Effects(watermark=fx.watermark), tts.device)
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
-                       join_kw=join_params(trim_db, keep_ms, fade_ms), speed=speed, pitch=pitch, silence=silence):
-        piece = grp.piece.reshape(1, -1)
-        if wms is None:
+                       join_kw=join_params(trim_db, keep_ms, fade_ms), fx=dataclasses.replace(fx, watermark=None)):
+        piece = mark.feed(grp.piece.reshape(1, -1))
+        if piece is not None:
             yield piece
-        elif piece.numel() > 0:
-            out, n = wms.feed(piece)
-            if n[0] > 0:
-                yield out[:, : n[0]]
-    if wms is not None:
-        out, n = wms.flush()
-        if n[0] > 0:
-            yield out[:, : n[0]]
+    piece = mark.flush()
+    if piece is not None:
+        yield piece

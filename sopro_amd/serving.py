@@ -32,9 +32,7 @@ class _Request:
     t_submit: float
     stream: Optional["_StreamSink"] = None  # submit_stream: where the lane puts this row's chunks
     seed: Optional[int] = None
-    speed: float = 1.0  # speaking rate of this request: applied after decoding, so it is no part of the batching key
-    pitch: float = 0.0  # semitones of this request: applied after decoding too
-    watermark: Any = None  # the mark of this request: applied last, one per row
+    fx: Any = None  # submit: this request's effects.Effects - applied after decoding, one per row, so no part of the batching key
     silence: Any = None  # the silence control of this request: applied after rate and pitch, one per row
 
 
@@ -123,32 +121,20 @@ class SynthesisService:
                text_ids: Optional[torch.Tensor] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
                **timing) -> "Future[torch.Tensor]":
         """Queue one utterance; the future resolves to the waveform ``[1, 1, N]`` on the device (``synthesize``'s result).
-        ``speed``: speaking rate in [0.5, 2.0] of this request (``mode="batch"`` only).  It is applied to the decoded batch, one
-        rate per row, so requests with different rates share a batch.  ``pitch``: semitones in [-12, 12] of this request, likewise
-        (``mode="batch"`` only, one pitch per row, no part of the batching key).  ``watermark``: a ``sopro_amd.Watermark`` for this
-        request (``mode="batch"`` only; the batch is marked in one launch, one mark per row, so tenants share a batch).  ``silence``: a ``sopro_amd.Silence`` for this
-        request (``mode="batch"`` only; the batch is squeezed in one launch sequence, one setting per row, no part of the batching
-        key).  The service has no word timing in either mode: a timing
-        keyword (``alignment``, ``word_cues``, ...) raises."""
-        from . import hip
+        ``speed``, ``pitch``, ``silence``, ``watermark`` (``sopro_amd.effects``; ``mode="batch"`` only): this request's own.  They are
+        applied to the decoded batch, one setting per row, so requests (and tenants) that differ in them share a batch.  The service
+        has no word timing in either mode: a timing keyword (``alignment``, ``word_cues``, ...) raises."""
+        from . import effects
         from .align import refuse_timing
-        from .silence import check_silence
-        from .streaming import refuse_pitch, refuse_silence, refuse_speed, refuse_watermark
-        from .watermark import check_mark
 
         refuse_timing(timing, f"SynthesisService(mode={'continuous' if self.engine is not None else 'batch'!r})")
         if timing:
             raise TypeError(f"submit() got unexpected keyword arguments {sorted(timing)}")
         if self._closed:
             raise RuntimeError("service is closed")
-        hip.prosody_step(speed, pitch)
-        check_mark(watermark)
-        check_silence(silence)
+        fx = effects.Effects.of(speed, pitch, silence, watermark)
         if self.engine is not None:
-            refuse_speed(speed, "SynthesisService(mode='continuous')")
-            refuse_pitch(pitch, "SynthesisService(mode='continuous')")
-            refuse_watermark(watermark, "SynthesisService(mode='continuous')")
-            refuse_silence(silence, "SynthesisService(mode='continuous')")
+            effects.refuse("SynthesisService(mode='continuous')", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
             self.stats["requests"] += 1
             return self.engine.submit(text=text, text_ids=text_ids, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                       anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames)
@@ -158,8 +144,7 @@ class SynthesisService:
         ss = float(style_strength if style_strength is not None else self.tts.cfg.style_strength)
         key = (int(max_frames), float(top_p), float(temperature), bool(anti_loop), ss, min_gen_frames)
         fut: Future = Future()
-        self._inbox.put(_Request(ids, ref, key, fut, time.perf_counter(), speed=float(speed), pitch=float(pitch), watermark=watermark,
-                                 silence=silence))
+        self._inbox.put(_Request(ids, ref, key, fut, time.perf_counter(), fx=fx))
         return fut
 
     def submit_stream(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
@@ -170,17 +155,13 @@ class SynthesisService:
         """Queue one streamed utterance -> a blocking iterator over its [1, n * 1920] chunks (``stream``'s chunks).  Streams with equal
         parameters are grouped into batches of up to ``max_batch`` rows (within ``max_wait_ms``) and each batch runs as one
         ``stream_batch`` on a lane, sharing the device with whole-utterance batches (AR lock per chunk, bulk lock for refinement and
-        decoding).  Closing or dropping the iterator drops the row from its batch.  Batched streams have no speaking-rate control:
-        ``speed`` other than 1.0 raises, and so do ``pitch`` other than 0.0, ``watermark`` other than None and ``silence`` other than
-        None."""
-        from .streaming import refuse_pitch, refuse_silence, refuse_speed, refuse_watermark
+        decoding).  Closing or dropping the iterator drops the row from its batch.  Batched streams have none of the four effects:
+        ``speed`` other than 1.0, ``pitch`` other than 0.0, ``watermark`` or ``silence`` other than None raises."""
+        from .effects import refuse
 
         if self._closed:
             raise RuntimeError("service is closed")
-        refuse_speed(speed, "submit_stream")
-        refuse_pitch(pitch, "submit_stream")
-        refuse_watermark(watermark, "submit_stream")
-        refuse_silence(silence, "submit_stream")
+        refuse("submit_stream", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
         if self.engine is not None:
             raise RuntimeError("submit_stream is not available in mode='continuous' (frame-level admission has no streaming path); "
                                "use mode='batch'")
@@ -205,18 +186,14 @@ class SynthesisService:
         split here and every segment goes through ``submit``, so the scheduler batches the segments with whatever else is queued;
         a small waiter thread gathers the segment futures in order, stacks them into one padded tensor and joins them on the
         device (``hip.join_segments``).  The sampler draws as ``submit`` draws (a fresh take per segment: no seed, no group plan).
-        ``speed``: every segment is submitted at this rate (stretched in its batch, before the join) and the pauses are divided by it.
-        ``pitch``: every segment is submitted at this pitch; the pauses are not touched by it.  ``watermark``: the segments are
-        submitted unmarked and the joined waveform is marked (``hip.wm_embed``), as in ``SoproTTS.synthesize_long``.  ``silence``:
-        every segment is submitted with it (squeezed in its batch, before the join)."""
-        from . import hip
+        ``speed``, ``pitch``, ``silence``: every segment is submitted with them (applied in its batch, before the join); the pauses are
+        divided by ``speed`` only.  ``watermark``: the segments are submitted unmarked and the joined waveform is marked, as in
+        ``SoproTTS.synthesize_long``."""
+        from . import effects, hip
         from .longform import LongformPart, LongformResult, join_params, pause_samples, scaled_pause, split_text
-        from .silence import check_silence
-        from .watermark import check_mark
 
-        hip.prosody_step(speed, pitch)
-        check_mark(watermark)
-        check_silence(silence)
+        fx = effects.Effects.of(speed, pitch, silence, watermark)
+        mark = effects.Effects(watermark=fx.watermark)
 
         if self._closed:
             raise RuntimeError("service is closed")
@@ -244,8 +221,8 @@ class SynthesisService:
                     for k, w in enumerate(wavs):
                         rows[k, : lens[k]] = w
                     out, edges, offs = hip.join_segments(rows, lens, gaps, **join_kw)
-                    if watermark is not None and out.numel() > 0:
-                        out = hip.wm_embed(out.reshape(1, -1), [int(out.numel())], watermark).reshape(-1)
+                    if not mark.plain and out.numel() > 0:
+                        out = effects.apply(out.reshape(1, -1), [int(out.numel())], [mark])[0].reshape(-1)
                         torch.cuda.current_stream(dev).synchronize()  # (the future's reader may be on another stream)
                 o, e = offs.tolist(), edges.tolist()
                 cues = [(segs[k].text, o[k], o[k] + e[k][1] - e[k][0]) for k in range(len(segs))]
@@ -327,8 +304,7 @@ class SynthesisService:
                 try:
                     out = lane.synthesize_batch([""] * len(batch), [r.ref for r in batch], max_frames=mf, top_p=top_p, temperature=temp,
                                                 anti_loop=anti, style_strength=ss, min_gen_frames=mg, text_ids=[r.text_ids for r in batch],
-                                                phase_locks=locks, speed=[r.speed for r in batch], pitch=[r.pitch for r in batch],
-                                                watermark=[r.watermark for r in batch], silence=[r.silence for r in batch])
+                                                phase_locks=locks, effects=[r.fx for r in batch])
                     self.stats["requests"] += len(batch)
                     self.stats["batches"] += 1
                     self.stats["rows"] += len(batch)

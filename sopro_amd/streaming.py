@@ -40,39 +40,13 @@ class SoproTTSStreamer:
                nar_context_frames: Optional[int] = None, min_gen_frames: Optional[int] = None,
                text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0,
                pitch: float = 0.0, watermark=None, silence=None) -> Iterator[torch.Tensor]:
-        """``speed`` (new): speaking rate in [0.5, 2.0].  Other than 1.0, every decoded chunk is fed to a ``hip.TimeStretchState``
-        and the blocks that became ready are yielded as [1, n * 480] (a step that completes no block yields nothing); a flush
-        after the last chunk yields the rest.  The concatenation is ``hip.time_stretch`` of the unstretched stream's
-        concatenation, bit for bit.  ``pitch`` (new): semitones in [-12, 12].  Other than 0.0, the chunks (stretched at
-        ``hip.prosody_step``'s step' where that is not the identity) are fed to a ``hip.PitchShiftState`` and the outputs whose
-        taps are in are yielded as [1, n]; both states are flushed after the last chunk.  The concatenation is
-        ``hip.apply_prosody`` of the plain stream's concatenation, bit for bit.  ``watermark`` (new): a ``sopro_amd.Watermark``.
-        The chunks (after the stretch and the resampler) are fed to a ``hip.WatermarkState`` and the 480-sample blocks whose
-        envelope is final are yielded; the state is flushed last.  The concatenation is ``hip.wm_embed`` of the unmarked stream's
-        concatenation, bit for bit.  ``silence`` (new): a ``sopro_amd.Silence``.  The chunks (after the stretch and the
-        resampler, before the watermark) are fed to a ``hip.SilenceState``: the silent lead-in is never yielded, sound is yielded at
-        once, the end of a long pause when sound resumes; the state is flushed after the last chunk.  The concatenation is
-        ``hip.silence_squeeze`` of the plain stream's concatenation, bit for bit."""
-        from . import hip
-        from .silence import check_silence
-        from .watermark import check_mark
+        """``speed``, ``pitch``, ``silence``, ``watermark`` (new): every decoded chunk goes through an ``effects.Chain`` and what is
+        ready of it is yielded as [1, n] (a step that completes nothing yields nothing); a flush after the last chunk yields the rest.
+        The concatenation is ``effects.apply`` of the plain stream's concatenation, bit for bit (``sopro_amd.effects``)."""
+        from .effects import Chain, Effects
 
         tts = self.tts
-        check_mark(watermark)
-        check_silence(silence)
-        step, inc = hip.prosody_step(speed, pitch)
-        tsm = hip.TimeStretchState(1, None, tts.device, steps=[step]) if step != hip.TSM_HS << 16 else None
-        psh = hip.PitchShiftState(1, None, tts.device, incs=[inc]) if inc != hip.PITCH_ONE else None
-        sil = hip.SilenceState(1, silence, tts.device) if silence is not None else None
-        wms = hip.WatermarkState(1, watermark, tts.device) if watermark is not None else None
-
-        def rate(wav: Optional[torch.Tensor], last: bool = False) -> Optional[torch.Tensor]:
-            for st in (tsm, psh, sil, wms):  # (a stage's flush feeds the next one before that is flushed)
-                if st is None or (wav is None and not last):
-                    continue
-                out, n = st.feed(wav, flush=last)
-                wav = out[:, : n[0]] if n[0] > 0 else None
-            return wav
+        chain = Chain.of(Effects.of(speed, pitch, silence, watermark), tts.device)
 
         model = tts.model
         ids = text_ids if text_ids is not None else tts.encode_text(text)
@@ -109,17 +83,16 @@ class SoproTTSStreamer:
                 break
             hist.append(int(tok))
             if len(hist) % cf == 0:
-                wav = rate(refine_and_emit(len(hist)))
+                wav = chain.feed(refine_and_emit(len(hist)))
                 if wav is not None:
                     yield wav
         if emitted < len(hist):
-            wav = rate(refine_and_emit(len(hist)))
+            wav = chain.feed(refine_and_emit(len(hist)))
             if wav is not None:
                 yield wav
-        if tsm is not None or psh is not None or sil is not None or wms is not None:
-            wav = rate(None, last=True)
-            if wav is not None:
-                yield wav
+        wav = chain.flush()
+        if wav is not None:
+            yield wav
 
 
 @torch.inference_mode()
@@ -128,48 +101,12 @@ def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_t
            pitch: float = 0.0, watermark=None, silence=None, **kwargs) -> Iterator[torch.Tensor]:
     """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch``, ``watermark`` and ``silence`` are new: see
     MimiStreamDecoder, SoproTTSStreamer.stream)"""
-    from . import hip
-    from .silence import check_silence
-    from .watermark import check_mark
+    from .effects import Effects
 
-    hip.prosody_step(speed, pitch)  # (a rate or a pitch out of range is refused here, not at the first chunk)
-    check_mark(watermark)
-    check_silence(silence)
+    Effects.of(speed, pitch, silence, watermark)  # (a bad value is refused here, not at the first chunk)
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
                            chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
-
-
-def refuse_speed(speed, what: str) -> None:
-    """The lockstep / frame-level paths have no speaking rate: anything but 1.0 is an error, never ignored."""
-    from . import hip
-
-    if hip.tsm_step(speed) != hip.TSM_HS << 16:
-        raise NotImplementedError(f"{what} has no speaking-rate control (speed={speed!r}): use stream(), synthesize_batch() or "
-                                  "SynthesisService.submit() in mode='batch'")
-
-
-def refuse_pitch(pitch, what: str) -> None:
-    """The lockstep / frame-level paths have no pitch control either: anything but 0.0 is an error, never ignored."""
-    from . import hip
-
-    if hip.pitch_inc(pitch) != hip.PITCH_ONE:
-        raise NotImplementedError(f"{what} has no pitch control (pitch={pitch!r}): use stream(), synthesize_batch() or "
-                                  "SynthesisService.submit() in mode='batch'")
-
-
-def refuse_watermark(watermark, what: str) -> None:
-    """The lockstep / frame-level paths have no watermark: anything but None is an error, never ignored."""
-    if watermark is not None:
-        raise NotImplementedError(f"{what} has no watermark (watermark={watermark!r}): use stream(), synthesize_batch() or "
-                                  "SynthesisService.submit() in mode='batch'")
-
-
-def refuse_silence(silence, what: str) -> None:
-    """The lockstep / frame-level paths have no silence control: anything but None is an error, never ignored."""
-    if silence is not None:
-        raise NotImplementedError(f"{what} has no silence control (silence={silence!r}): use stream(), synthesize_batch() or "
-                                  "SynthesisService.submit() in mode='batch'")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -230,11 +167,11 @@ def stream_batch(tts, texts: Sequence[str], refs: Sequence, *, chunk_frames: int
     ``seeds``: one per row (None: a fresh take for that row).  ``phase_locks`` = (AR lock, bulk lock): held around the AR advance and
     around refinement + decode of every step (a serving lane shares its device with whole-utterance batches).  ``timings``: seconds
     of host wall time accumulated under "ar", "refine", "decode".  ``alive(b)`` (a server): False once row b's consumer has gone - the
-    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0, ``watermark``: only None, ``silence``: only None (batched streams have none of the four)."""
-    refuse_speed(speed, "stream_batch")
-    refuse_pitch(pitch, "stream_batch")
-    refuse_watermark(watermark, "stream_batch")
-    refuse_silence(silence, "stream_batch")
+    row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0,
+    ``watermark``, ``silence``: only None (batched streams have none of the four effects)."""
+    from .effects import refuse
+
+    refuse("stream_batch", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
     model = tts.model
     B = len(texts)
     if B == 0 or len(refs) != B:

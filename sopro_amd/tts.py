@@ -133,23 +133,11 @@ class SoproTTS:
                    silence=None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
-        draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed`` (new): speaking rate
-        in [0.5, 2.0], applied to the decoded waveform by ``hip.time_stretch`` (pitch-preserving; 1.0 launches nothing).
-        ``pitch`` (new): semitones in [-12, 12], applied to the decoded waveform as a stretch by rho = 2^(pitch / 12) and a
-        band-limited resample that reads rho times as fast (``hip.prosody_step``, ``hip.pitch_shift``): the duration stays what
-        ``speed`` makes it and every frequency - formants included - is multiplied by rho; 0.0 launches nothing.  ``speed / rho``
-        must lie in [0.5, 2.0].  ``watermark`` (new): a ``sopro_amd.Watermark`` (key, tag, strength) added to the waveform as the
-        last step, after rate and pitch (``hip.wm_embed``; see ``sopro_amd.watermark`` for what the mark survives); None launches
-        nothing.  ``silence`` (new): a ``sopro_amd.Silence``; pauses longer than its cap are squeezed, the silent lead-in and the tail
-        are trimmed (``hip.silence_squeeze``), after rate and pitch - its times are heard time - and before the watermark; None
-        launches nothing."""
-        from . import hip
-        from .silence import check_silence
-        from .watermark import check_mark
+        draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed``, ``pitch``, ``silence``,
+        ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched."""
+        from . import effects
 
-        check_mark(watermark)
-        check_silence(silence)
-        step, inc = hip.prosody_step(speed, pitch)
+        fx = effects.Effects.of(speed, pitch, silence, watermark)
         text_ids = self.encode_text(text)
         if ref is None:
             ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
@@ -160,14 +148,7 @@ class SoproTTS:
         wav = self.codec.decode_full(tokens)
         if wav.numel() == 0:
             return wav
-        if not hip.is_plain([(step, inc)]):
-            out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
-            wav = out.reshape(1, 1, -1)
-        if silence is not None:
-            wav = hip.silence_squeeze(wav.reshape(1, -1), [int(wav.shape[-1])], silence)[0].reshape(1, 1, -1)
-        if watermark is not None and wav.numel() > 0:
-            wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
-        return wav
+        return effects.apply(wav.reshape(1, -1), [int(wav.shape[-1])], [fx])[0].reshape(1, 1, -1)
 
     @torch.inference_mode()
     def synthesize_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, max_frames: int = 400,
@@ -178,44 +159,31 @@ class SoproTTS:
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
                          speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
                          align_heads=None, pitch: Union[float, Sequence[float]] = 0.0,
-                         watermark=None, silence=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         watermark=None, silence=None, effects=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
         ``PaddedBatch`` of ``wav`` [B, T * 1920], ``lens`` (valid samples per row) and ``tokens`` [B, T, Q] (a copy: the engine's
         own token matrix is overwritten by the next pass); the list above is ``[wav[b, :lens[b]].reshape(1, 1, -1)]``.
-        ``speed``: speaking rate in [0.5, 2.0], one float or one per row; the decoder's padded batch is stretched in one launch
-        on the bulk stream before it is sliced (``hip.time_stretch``), so ``PaddedBatch.wav`` / ``lens`` are the stretched rows
-        and ``tokens`` stay what the model produced.  All rows at 1.0: nothing is launched.
-        ``pitch``: semitones in [-12, 12], one float or one per row (see ``synthesize``); the stretched batch is resampled in one
-        more launch (``hip.pitch_shift``) before it is sliced.  All rows at 0.0: nothing is launched, and a row at 0.0 among
-        shifted ones comes back bit for bit.
+        ``speed``, ``pitch``, ``silence``, ``watermark``: one value or one per row each (None entries allowed in the last two), see
+        ``sopro_amd.effects``; the decoder's padded batch goes through the chain on the bulk stream before it is sliced, so
+        ``PaddedBatch.wav`` / ``lens`` are the finished rows and ``cuts`` their cut tables (None without ``silence``), while ``tokens``
+        and ``frames`` stay what the model produced.
         ``alignment``: a sink like ``timings`` - a list passed in is filled with one ``align.Alignment`` per row (frame -> text
         position path, frame range per position, confidence; in frames, before any stretch) by a post-pass on the bulk stream
         (``model.align_batch``: the AR stack replayed over the generated tokens, ``hip.align_scores`` / ``hip.align_paths``);
         ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched.
-        ``watermark``: one ``sopro_amd.Watermark`` or None, or one per row with None entries allowed; the padded batch (stretched and
-        shifted where asked) is marked in one launch on the bulk stream before it is sliced (``hip.wm_embed``), so ``PaddedBatch.wav``
-        is marked.  All rows None: nothing is launched, and a row at None among marked ones comes back bit for bit.
-        ``silence``: one ``sopro_amd.Silence`` or None, or one per row with None entries allowed; the padded batch (stretched and
-        shifted where asked) is squeezed in one launch sequence on the bulk stream before it is marked and sliced
-        (``hip.silence_squeeze``): ``PaddedBatch.wav`` / ``lens`` are the squeezed rows, ``cuts`` their cut tables, ``tokens`` and
-        ``frames`` stay what the model produced.  All rows None: nothing is launched, and a row at None among squeezed ones comes
-        back bit for bit."""
+        ``effects`` (internal): the rows' ``effects.Effects`` as they are, instead of the four keywords."""
         import contextlib
         import time
 
-        from . import hip
-        from .silence import per_row as sil_per_row
-        from .watermark import per_row
+        from . import effects as E
 
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
-        sils = sil_per_row(silence, len(ids))
-        squeezed = any(s is not None for s in sils)
-        marks = per_row(watermark, len(ids))
-        marked = any(m is not None for m in marks)
-        prosody = hip.prosody_steps(speed, pitch, len(ids))
-        stretch = not hip.is_plain(prosody)  # (a rate, a pitch or both)
+        # (a bad value is refused before anything runs)
+        fxs = list(effects) if effects is not None else E.per_row(speed, pitch, silence, watermark, len(ids))
+        if len(fxs) != len(ids):
+            raise ValueError(f"effects: one per row ({len(ids)}), got {len(fxs)}")
         if alignment is not None:
             self.model._align_heads(align_heads)  # (a bad selection is refused before anything runs)
         locks = tuple(phase_locks) if phase_locks is not None else ()
@@ -293,18 +261,11 @@ class SoproTTS:
             if alignment is not None:  # (queued behind the decoder on the bulk stream)
                 alignment[:] = self.model.align_batch(state["prep"], state, heads=align_heads)
             hop = int(self.codec.mc.frame_samples)
-            n_samples = [n * hop for n in lens]
-            if stretch:  # (rows at 1.0 / 0.0 in a mixed batch come back bit for bit: both operators are the identity there)
-                wav, n_samples = hip.apply_prosody(wav, n_samples, prosody)
-            cuts = None
-            if squeezed:  # (after rate and pitch: the cap is heard time; before the mark, which does not survive interior cuts)
-                wav, n_samples, cuts = hip.silence_squeeze(wav, n_samples, sils)
-            if marked:  # (last: the mark does not survive a stretch or a resample)
-                wav = hip.wm_embed(wav, n_samples, marks)
+            wav, n_samples, cuts = E.apply(wav, [n * hop for n in lens], fxs)
             toks = None
             if padded:  # (the engine's own token matrix: copied before the next pass overwrites it, complete before any stream reads it)
                 toks = codes.long()
-            if padded or stretch or marked or squeezed:
+            if padded or not all(fx.plain for fx in fxs):
                 self.model.bulk_stream.synchronize()
         if padded:
             return PaddedBatch(wav, n_samples, toks, lens, cuts)
@@ -319,22 +280,15 @@ class SoproTTS:
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
-        ``align.Alignment`` with its ``confidence``.  Cues are whole frames (1920 samples); with ``speed`` other than 1.0 they are
-        mapped by ``align.map_speed`` (accurate to +-240 samples, the stretch's search radius), with ``pitch`` other than 0.0 by
-        ``align.stretch_cues`` at the stretch's own step and then ``align.shift_cues`` (+-240 / 2^(pitch / 12) samples: see there).
+        ``align.Alignment`` with its ``confidence``.  Cues are whole frames (1920 samples) and follow the audio through ``speed``,
+        ``pitch`` and ``silence`` (``effects.map_cues`` has their accuracy); the mark changes no length, so it moves no cue.
         ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
-        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12).  ``watermark``: as
-        in ``synthesize``; the mark changes no length, so the cues do not move.  ``silence``: as in ``synthesize``; the cues go
-        through speed, pitch and then ``align.squeeze_cues`` with the operator's own cut table (exact)."""
+        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12)."""
         from . import align as A
-        from . import hip
-        from .silence import check_silence
-        from .watermark import check_mark
+        from . import effects
 
-        check_mark(watermark)
-        check_silence(silence)
-        step, inc = hip.prosody_step(speed, pitch)
+        fx = effects.Effects.of(speed, pitch, silence, watermark)
         text_ids = self.encode_text(text)
         spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
         if len(spans) != int(text_ids.numel()):
@@ -348,19 +302,10 @@ class SoproTTS:
             min_gen_frames=min_gen_frames, seed=seed, alignment=sink, align_heads=align_heads)[0]
         wav = self.codec.decode_full(tokens)
         words = A.word_cues(text, spans, sink[0].token_frames, hop=int(self.codec.mc.frame_samples))
-        if not hip.is_plain([(step, inc)]) and wav.numel() > 0:
-            out, _ = hip.apply_prosody(wav.reshape(1, -1), [int(wav.shape[-1])], [(step, inc)])
+        if wav.numel() > 0:
+            out, _, cuts = effects.apply(wav.reshape(1, -1), [int(wav.shape[-1])], [fx])
             wav = out.reshape(1, 1, -1)
-            if step != hip.TSM_HS << 16:
-                words = A.stretch_cues(words, step)
-            if inc != hip.PITCH_ONE:
-                words = A.shift_cues(words, inc)
-        if silence is not None and wav.numel() > 0:
-            out, _, cuts = hip.silence_squeeze(wav.reshape(1, -1), [int(wav.shape[-1])], silence)
-            wav = out.reshape(1, 1, -1)
-            words = A.squeeze_cues(words, cuts[0])
-        if watermark is not None and wav.numel() > 0:
-            wav = hip.wm_embed(wav.reshape(1, -1), [int(wav.shape[-1])], watermark).reshape(1, 1, -1)
+            words = effects.map_cues(words, fx, cuts[0] if cuts is not None else None)
         return A.TimedResult(wav, words, sink[0])
 
     def clone_lane(self) -> "SoproTTS":
@@ -369,15 +314,10 @@ class SoproTTS:
 
     def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
                **kwargs) -> Iterator[torch.Tensor]:
-        """reference: src/sopro/model.py:577-580.  ``speed`` (new): speaking rate in [0.5, 2.0]; every decoded chunk goes through
-        the chunked time stretch and the blocks that are ready are yielded as [1, n * 480] (see streaming.SoproTTSStreamer.stream).
-        ``pitch`` (new): semitones in [-12, 12]; the chunks then also go through the chunked resampler and come out as [1, n].
-        ``watermark`` (new): a ``sopro_amd.Watermark``; every chunk goes through a ``hip.WatermarkState`` last, so a chunk comes out
-        up to 1440 samples short and the rest follows (flushed at the end).  The concatenation is ``hip.wm_embed`` of the unmarked
-        stream's concatenation, bit for bit.  ``silence`` (new): a ``sopro_amd.Silence``; the chunks go through a
-        ``hip.SilenceState`` after rate and pitch and before the watermark: the silent lead-in is never yielded, sound comes out at
-        once, the end of a long pause when sound resumes.  The concatenation is ``hip.silence_squeeze`` of the plain stream's
-        concatenation, bit for bit."""
+        """reference: src/sopro/model.py:577-580.  ``speed``, ``pitch``, ``silence``, ``watermark`` (new): every decoded chunk goes
+        through the chunked chain of ``sopro_amd.effects`` and what is ready is yielded as [1, n] (with a watermark a chunk comes out
+        up to 1440 samples short and the rest follows); the concatenation is ``synthesize``'s chain over the plain stream's
+        concatenation, bit for bit (see streaming.SoproTTSStreamer.stream)."""
         from .align import refuse_timing
         from .streaming import stream
 
@@ -392,17 +332,14 @@ class SoproTTS:
                      **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
         entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
-        A speaking rate or a pitch is not available here (``speed`` other than 1.0 or ``pitch`` other than 0.0 raises): use
-        ``stream`` or ``synthesize_batch``.  Neither is a watermark (``watermark`` other than None raises) or silence control
-        (``silence`` other than None raises)."""
+        None of the four effects is available here (``speed`` other than 1.0, ``pitch`` other than 0.0, ``watermark`` or ``silence``
+        other than None raises): use ``stream`` or ``synthesize_batch``."""
+        from . import effects
         from .align import refuse_timing
-        from .streaming import refuse_pitch, refuse_silence, refuse_speed, refuse_watermark, stream_batch
+        from .streaming import stream_batch
 
         refuse_timing(kwargs, "stream_batch")
-        refuse_speed(speed, "stream_batch")
-        refuse_pitch(pitch, "stream_batch")
-        refuse_watermark(watermark, "stream_batch")
-        refuse_silence(silence, "stream_batch")
+        effects.refuse("stream_batch", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
                             cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, pitch=pitch,
@@ -417,14 +354,12 @@ class SoproTTS:
         (``trim_db=None``: nothing is trimmed), pauses follow the kind of boundary (``pauses_ms``), cuts get ``fade_ms`` raised-cosine
         fades.  ``max_frames`` and the sampling parameters are per segment, as in ``synthesize``; segment k draws as
         ``synthesize(segment_k, ref=ref, seed=seed + k)`` does.  ``keep_parts=True`` also returns every segment's untrimmed
-        waveform and tokens (``parts``) and the kept range (``edges``).  ``speed``: speaking rate in [0.5, 2.0]; every group's
-        padded batch is stretched before the join (``parts`` are the stretched rows, cue times refer to the stretched audio) and
-        the pauses are divided by it.  ``pitch``: semitones in [-12, 12]; every group's batch is stretched and resampled before the
-        join (see ``synthesize``), the pauses are not touched by it.  ``word_cues=True`` also fills ``words`` (one ``align.LongWordCue`` per word, samples in the
-        joined waveform).  ``watermark``: a ``sopro_amd.Watermark``; the batches run unmarked and the joined waveform is marked in one
-        launch, so the carrier's phase is continuous across the segments (``parts`` stay unmarked).  ``silence``: a
-        ``sopro_amd.Silence``; every group's batch is squeezed before the join (``parts`` are the squeezed rows), so the pauses the
-        join puts between sentences are untouched; word cues go through ``align.squeeze_cues`` first.  Full parameter list:
+        waveform and tokens (``parts``) and the kept range (``edges``).  ``word_cues=True`` also fills ``words`` (one
+        ``align.LongWordCue`` per word, samples in the joined waveform).  ``speed``, ``pitch``, ``silence`` (``sopro_amd.effects``): every group's padded batch goes through them
+        before the join, so ``parts`` are the finished rows, cue times refer to the audio as it is heard and the pauses the join puts
+        between sentences are untouched by the squeeze; the pauses are divided by ``speed`` and not touched by ``pitch``.
+        ``watermark``: the batches run unmarked and the joined waveform is marked in one launch, so the carrier's phase is continuous
+        across the segments (``parts`` stay unmarked).  Full parameter list:
         ``longform.synthesize_long``."""
         from .longform import synthesize_long
 
@@ -435,19 +370,15 @@ class SoproTTS:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
         segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed`` and ``pitch``).
-        ``watermark``: the pieces go through one ``hip.WatermarkState`` (a piece comes out up to 1440 samples short, the rest follows,
+        ``watermark``: the pieces go through one chunked mark (a piece comes out up to 1440 samples short, the rest follows,
         and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit.
         ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
-        from . import hip
         from .align import refuse_timing
+        from .effects import Effects
         from .longform import stream_long
-        from .silence import check_silence
-        from .watermark import check_mark
 
         refuse_timing(kwargs, "stream_long")
-        hip.prosody_step(speed, pitch)  # (refused here, not at the first piece)
-        check_mark(watermark)
-        check_silence(silence)
+        Effects.of(speed, pitch, silence, watermark)  # (refused here, not at the first piece)
         return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
     def detect_watermark(self, wav, key: int):

@@ -237,14 +237,14 @@ def test_silence_is_keyword_only_with_default_none_everywhere():
 
 
 def test_refusing_paths_raise_before_anything_runs():
-    from sopro_amd import streaming
+    from sopro_amd import effects, streaming
     from sopro_amd.serving import SynthesisService
     from sopro_amd.tts import SoproTTS
 
     s = S.Silence()
-    streaming.refuse_silence(None, "x")
+    effects.refuse("x", silence=None)
     with pytest.raises(NotImplementedError):
-        streaming.refuse_silence(s, "stream_batch")
+        effects.refuse("stream_batch", silence=s)
     with pytest.raises(NotImplementedError):
         next(iter(streaming.stream_batch(None, ["a"], [None], silence=s)))
     with pytest.raises(NotImplementedError):

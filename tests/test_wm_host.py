@@ -214,14 +214,14 @@ def test_watermark_is_keyword_only_with_default_none_everywhere():
 
 
 def test_refusing_paths_raise_before_anything_runs():
-    from sopro_amd import streaming
+    from sopro_amd import effects, streaming
     from sopro_amd.serving import SynthesisService
     from sopro_amd.tts import SoproTTS
 
     m = wm.Watermark(KEY, TAG)
-    streaming.refuse_watermark(None, "x")
+    effects.refuse("x", watermark=None)
     with pytest.raises(NotImplementedError):
-        streaming.refuse_watermark(m, "stream_batch")
+        effects.refuse("stream_batch", watermark=m)
     with pytest.raises(NotImplementedError):
         next(iter(streaming.stream_batch(None, ["a"], [None], watermark=m)))
     with pytest.raises(NotImplementedError):

@@ -377,6 +377,8 @@ int sopro_rvq_assign_f32(const float* scores, int64_t lds, int32_t V, const floa
 /* softmax(q k^T * scale + mask) v, fp32, heads interleaved in the row ([.., H*dh]).
  * klens[b] (NULL = Tk) masks keys >= klens[b]; causal != 0 additionally keeps only keys with
  * q_abs - window < k_abs <= q_abs where q_abs = q_pos0 + tq, k_abs = k_pos0 + tk.
+ * A row (b, tq) that sees no key at all - klens[b] <= 0, or a causal window that holds none of the Tk keys - is written as
+ * zeros (never NaN), by all three entry points below.
  * dh in {64, 96, 192}.  Replaces F.scaled_dot_product_attention at src/sopro/nn/text.py:118-126,
  * src/sopro/nn/ref.py:88-96 and HF:modeling_mimi.py:657-726 (sliding window :882-888). */
 typedef struct sopro_attn_args {
@@ -403,7 +405,8 @@ int sopro_attn_decode_f32(const sopro_attn_args* args, void* stream);
 /* The whole cached text cross-attention block of the AR frame in one launch (src/sopro/nn/text.py:85-132) on
  * per-utterance folded operands Kp[b,h] = K_h Wq_h and Vp[b,h] = V_h Wo_h^T (both [S_cap, D], D == 384):
  * Y[h][b] = (h == 0 ? Xin[b] : 0) + gate * sum_k softmax_k(<RMSNorm(Xin[b]), Kp[b,h,k]> * scale) * Vp[b,h,k],
- * Xin = X + sum_{s<np} Xp[s].  The H partial outputs (y_part_stride apart) are summed by the next kernel. */
+ * Xin = X + sum_{s<np} Xp[s].  The H partial outputs (y_part_stride apart) are summed by the next kernel.
+ * A row without keys (klens[b] <= 0) passes its input through: Y[0][b] = Xin[b] and Y[h > 0][b] = 0, exactly. */
 typedef struct sopro_xattn_args {
   const float* X; int64_t ldx;
   const float* Xp; int64_t xp_stride;

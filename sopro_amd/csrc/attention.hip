@@ -518,10 +518,19 @@ __global__ __launch_bounds__(512) void xattn_step_kernel(const sopro_xattn_args 
     o4.x = o4.x * alpha + acc.x; o4.y = o4.y * alpha + acc.y; o4.z = o4.z * alpha + acc.z; o4.w = o4.w * alpha + acc.w;
     __syncthreads();  // sc / ps / red are rewritten by the next tile
   }
+  if (klen <= 0 && h == 0 && tid < 96) {
+    // a row without keys never entered the loop that stages its input: the residual slice is Xin[b] itself (same sum order)
+    float4 xv = *reinterpret_cast<const float4*>(a.X + (int64_t)b * a.ldx + tid * 4);
+    for (int s = 0; s < a.np; ++s) {
+      const float4 pv = *reinterpret_cast<const float4*>(a.Xp + (int64_t)s * a.xp_stride + (int64_t)b * a.ldx + tid * 4);
+      xv.x += pv.x; xv.y += pv.y; xv.z += pv.z; xv.w += pv.w;
+    }
+    *reinterpret_cast<float4*>(xsum + tid * 4) = xv;  // read back by the same thread below
+  }
   if (vg < 4) *reinterpret_cast<float4*>(&opart[vg][vd4 * 4]) = o4;
   __syncthreads();
   if (tid < 96) {
-    const float inv = l_run > 0.f ? a.gate / l_run : 0.f;
+    const float inv = l_run > 0.f ? a.gate / l_run : 0.f;  // no key: the attention term is exactly 0
     float4 y;
     const float4 p0 = *reinterpret_cast<const float4*>(&opart[0][tid * 4]);
     const float4 p1 = *reinterpret_cast<const float4*>(&opart[1][tid * 4]);

@@ -1122,11 +1122,21 @@ int sopro_nar_refine(sopro_engine* e, void* workspace, const float* cond, int64_
 }
 
 // ------------------------------------------------------------------------------------------------ Mimi decode
+// One SEANet level: a transposed convolution (ch -> co channels, rows -> orow = rows * r rows), then a residual block through `hid`
+// channels; the last level ends in the final convolution instead.  Computed once per call (sea_levels): the carve, the zero-row
+// fills and the launches all read the same array.
+struct SeaLevel {
+  int ch, co, rows, orow, r, hid;
+  bool last;
+  bool fused;   // the last level as ONE kernel (seanet_uptail): its 64-channel activation stays on the CU, so it has no raw buffer
+  bool res128;  // the residual block is the fused 128-channel kernel (seanet_res128)
+};
 struct MimiWs {
   int32_t* tok;
   float *emb, *q, *X, *y, *qkv, *ao, *hd, *e0, *hraw[8], *hact[8], *y1[8];
   float* lnst;  // (mean, squared deviations) per transformer row and 64-column group (fused LayerNorm)
   SplitK sk;
+  SeaLevel lv[8];
 };
 // bf16 mode (round 4): the SEANet decoder's activations - everything from the first convolution's output on - live in memory as
 // bf16 rows (SOPRO_MIMI_BF16=0: fp32 rows with operands rounded in flight, the round-3 form); the transformer stream stays fp32.
@@ -1141,6 +1151,32 @@ static bool mimi_half(const sopro_engine* e) {
 static bool seanet_fused(int B, int rows) {
   static const bool off = SOPRO_DEV_ENV("SOPRO_SEANET_FUSE") != nullptr && SOPRO_DEV_ENV("SOPRO_SEANET_FUSE")[0] == '0';
   return !off && (int64_t)B * rows >= 512 * 1024;
+}
+
+static void sea_levels(const sopro_engine_cfg& c, int B, int T, SeaLevel* lv) {
+  int ch = c.mimi_num_filters << c.mimi_n_ratios, rows = 2 * T;
+  for (int si = 0; si < c.mimi_n_ratios; ++si) {
+    SeaLevel& l = lv[si];
+    l.ch = ch; l.co = ch / 2; l.rows = rows; l.r = c.mimi_ratios[si]; l.orow = rows * l.r; l.hid = l.co / c.mimi_compress;
+    l.last = si + 1 == c.mimi_n_ratios;
+    l.fused = l.last && ch == 128 && l.r == 4 && seanet_fused(B, rows);
+    l.res128 = l.co == 128 && l.hid == 64;
+    ch = l.co; rows = l.orow;
+  }
+}
+
+// How a SEANet activation lies in memory; the values are sopro_gemm_split_ext.a_format.  Split form is [32 hi | 32 lo] bf16 per 32
+// channels: the same bytes, lines and strides as fp32 rows.
+enum ActFmt { ACT_F32 = 0, ACT_SPLIT = 1, ACT_BF16 = 2 };
+enum ActOut { OUT_RAW = 0, OUT_ACT = 1, OUT_RAW_ACT = 2 };  // an epilogue writes the raw rows, ELU(.) of them, or the raw rows plus an activated copy
+// sopro_gemm_split_ext.c_mode of a producer (raw rows are never in split form: only activated tensors are handed over that way)
+static int act_c_mode(ActOut what, ActFmt f) {
+  static const int mode[3][3] = {{0, 3, 4}, {0, 1, 2}, {6, 7, 8}};
+  return mode[f][what];
+}
+// p advanced by n elements of the format (bf16 rows: 2-byte elements behind a float pointer)
+static float* act_at(float* p, ActFmt f, size_t n) {
+  return f == ACT_BF16 ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(p) + n) : p + n;
 }
 
 static size_t mimi_carve(const sopro_engine* e, MimiWs& w, void* ws, int B, int T) {
@@ -1160,17 +1196,15 @@ static size_t mimi_carve(const sopro_engine* e, MimiWs& w, void* ws, int B, int 
   w.ao = cv.take<float>((size_t)B * N2 * HS);
   w.hd = cv.take<float>((size_t)B * N2 * c.mimi_inter);
   w.lnst = cv.take<float>((size_t)B * N2 * ((HS + 63) / 64) * 2);
-  size_t ch = (size_t)c.mimi_num_filters << c.mimi_n_ratios, rows = N2;
-  w.e0 = act(cv, (size_t)B * (1 + rows) * ch);
+  sea_levels(c, B, T, w.lv);
+  w.e0 = act(cv, (size_t)B * (1 + N2) * ((size_t)c.mimi_num_filters << c.mimi_n_ratios));
   for (int si = 0; si < c.mimi_n_ratios; ++si) {
-    const size_t co = ch / 2, orow = rows * c.mimi_ratios[si];
+    const SeaLevel& l = w.lv[si];
     // (the last level's 64-channel activation stays on the CU when the level runs as one kernel - seanet_uptail: no buffer for it;
     // it was 6.3 GB of a 64 x 200-frame call's 19 GB)
-    const bool on_cu = si + 1 == c.mimi_n_ratios && ch == 128 && c.mimi_ratios[si] == 4 && seanet_fused(B, (int)rows);
-    w.hraw[si] = on_cu ? nullptr : act(cv, (size_t)B * (2 + orow) * co);
-    w.hact[si] = si + 1 < c.mimi_n_ratios ? act(cv, (size_t)B * (2 + orow) * co) : nullptr;
-    w.y1[si] = si + 1 < c.mimi_n_ratios ? act(cv, (size_t)B * orow * (co / c.mimi_compress)) : nullptr;
-    ch = co; rows = orow;
+    w.hraw[si] = l.fused ? nullptr : act(cv, (size_t)B * (2 + l.orow) * l.co);
+    w.hact[si] = l.last ? nullptr : act(cv, (size_t)B * (2 + l.orow) * l.co);
+    w.y1[si] = l.last ? nullptr : act(cv, (size_t)B * l.orow * l.hid);
   }
   return cv.off;
 }
@@ -1223,24 +1257,14 @@ static int transformer_stack(sopro_engine* e, hipStream_t s, const char* pre, fl
     a.Q = w.qkv; a.ldq = 3 * HS; a.q_bstride = (int64_t)n * 3 * HS;
     a.O = w.ao; a.ldo = HS; a.o_bstride = (int64_t)n * HS;
     a.B = B; a.H = H; a.dh = dh; a.Tq = n; a.causal = 1; a.window = c.mimi_window; a.scale = 1.0f / sqrtf((float)dh);
-    if (sbt) {
-      // the batched streaming cache (all utterances in lockstep: one kv_len, one position): ONE launch appends every utterance's
-      // (k | v) rows and, under the evicting policy, writes the rows the next call keeps into the other half; the attention then
-      // reads utterance b's keys / values cap_rows rows apart in the current half
-      const int64_t bst = (int64_t)sbt->cap_rows * 2 * HS;
-      float* cache = sbt->kv + (size_t)(l * 2 + sbt->half) * sbt->rows_cap * bst;
-      float* other = sbt->kv + (size_t)(l * 2 + (sbt->half ^ 1)) * sbt->rows_cap * bst;
-      const int Tk = sbt->kv_len + n;
-      const int nkeep = (sbt->evict && Tk > c.mimi_window - 1) ? c.mimi_window - 1 : 0;
-      STG(sopro_stream_batch_append(cache, other, w.qkv, HS, B, bst, n, sbt->kv_len, nkeep, s));
-      a.K = cache; a.ldk = 2 * HS; a.k_bstride = bst;
-      a.V = cache + HS; a.ldv = 2 * HS; a.v_bstride = bst;
-      a.Tk = Tk; a.q_pos0 = past; a.k_pos0 = past + n - Tk;
-    } else if (!sst) {
+    const int keep = c.mimi_window - 1;  // rows a sliding-window layer hands to the next call
+    const float* kept = nullptr;         // single stream, evicting policy: those rows, moved to the other half AFTER the attention
+    float* kept_to = nullptr;
+    if (!sst && !sbt) {
       a.K = w.qkv + HS; a.ldk = 3 * HS; a.k_bstride = (int64_t)n * 3 * HS;
       a.V = w.qkv + 2 * HS; a.ldv = 3 * HS; a.v_bstride = (int64_t)n * 3 * HS;
       a.Tk = n;
-    } else {
+    } else if (sst) {
       // keys / values of earlier calls (post-RoPE) followed by this call's: append the (k | v) rows to the layer's cache
       float* cache = sst->kv + ((size_t)(l * 2 + sst->half) * sst->cap_rows) * 2 * HS;
       STG(sopro_copy2d_u32(cache + (size_t)sst->kv_len * 2 * HS, 2 * HS, w.qkv + HS, 3 * HS, n, 2 * HS, s));
@@ -1250,16 +1274,26 @@ static int transformer_stack(sopro_engine* e, hipStream_t s, const char* pre, fl
       a.q_bstride = a.o_bstride = 0;
       // what the next call sees: sliding-window layers keep the last window-1 positions (moved to the other half of the
       // layer's buffer), plain layers everything
-      if (sst->evict && Tk > c.mimi_window - 1) {
-        const int keep = c.mimi_window - 1;
-        float* other = sst->kv + ((size_t)(l * 2 + (sst->half ^ 1)) * sst->cap_rows) * 2 * HS;
-        STG(attend(a, s, attn_split));
-        STG(sopro_copy2d_u32(other, 2 * HS, cache + (size_t)(Tk - keep) * 2 * HS, 2 * HS, keep, 2 * HS, s));
-        goto attended;
+      if (sst->evict && Tk > keep) {
+        kept = cache + (size_t)(Tk - keep) * 2 * HS;
+        kept_to = sst->kv + ((size_t)(l * 2 + (sst->half ^ 1)) * sst->cap_rows) * 2 * HS;
       }
+    } else {
+      // the batched streaming cache (all utterances in lockstep: one kv_len, one position): ONE launch appends every utterance's
+      // (k | v) rows and, under the evicting policy, writes the rows the next call keeps into the other half; the attention then
+      // reads utterance b's keys / values cap_rows rows apart in the current half
+      const int64_t bst = (int64_t)sbt->cap_rows * 2 * HS;
+      float* cache = sbt->kv + (size_t)(l * 2 + sbt->half) * sbt->rows_cap * bst;
+      float* other = sbt->kv + (size_t)(l * 2 + (sbt->half ^ 1)) * sbt->rows_cap * bst;
+      const int Tk = sbt->kv_len + n;
+      const int nkeep = (sbt->evict && Tk > keep) ? keep : 0;
+      STG(sopro_stream_batch_append(cache, other, w.qkv, HS, B, bst, n, sbt->kv_len, nkeep, s));
+      a.K = cache; a.ldk = 2 * HS; a.k_bstride = bst;
+      a.V = cache + HS; a.ldv = 2 * HS; a.v_bstride = bst;
+      a.Tk = Tk; a.q_pos0 = past; a.k_pos0 = past + n - Tk;
     }
     STG(attend(a, s, attn_split));
-  attended:;
+    if (kept_to) STG(sopro_copy2d_u32(kept_to, 2 * HS, kept, 2 * HS, keep, 2 * HS, s));
     G og; og.sk = &w.sk; og.M = B * n; og.N = HS; og.K = HS; og.epi = SOPRO_EPI_RES; og.R = w.X + (size_t)PADX * HS; og.scale = F(e, p + ".ls1");
     og.c_seg = xs; og.r_seg = xs; og.rows_per_seg = n;
     if (fused_ln) { og.ln_stats_out = lnst; og.a_seg = (int64_t)n * HS; }
@@ -1300,18 +1334,24 @@ static int mimi_decode_core(sopro_engine* e, void* workspace, const int32_t* tok
   SOPRO_CHECK_ARG(c.mimi_res_kernel == 3 && c.mimi_last_kernel == 3 && c.mimi_compress == 2, "the SEANet sequence is written for k = 3 residual / last convs, compress 2");
   MimiWs w;
   mimi_carve(e, w, workspace, B, T);
+  const SeaLevel* lv = w.lv;
+  const int nl = c.mimi_n_ratios;
+  // bf16 mode: every activation of the SEANet decoder as bf16 rows in memory (strides then count bf16 elements): the first convolution
+  // reads the fp32 transformer stream and writes ELU(.) as bf16, every later contraction reads and writes bf16 rows (staged by plain
+  // copies), the fused kernels of the two 24 kHz-side levels have bf16-row forms.  Accumulation, bias, ELU and the skip additions are
+  // fp32.  `rowf` is the format of the raw rows and of every buffer's element size; activated tensors may be in split form instead.
+  const bool half = mimi_half(e);
+  const ActFmt rowf = half ? ACT_BF16 : ACT_F32;
   if (w.sk.ws) BODY(sopro_fill2d_u32(w.sk.tickets, SPLITK_TICKETS, 1, SPLITK_TICKETS, 0u, s));
   // the zero rows in front of every segment of a convolution input are never written by the kernels: clear just those
   {
     BODY(sopro_fill2d_u32(w.X, (int64_t)(PADX + N2) * HS, B, PADX * HS, 0u, s));
-    size_t chz = (size_t)c.mimi_num_filters << c.mimi_n_ratios, rowz = (size_t)N2;
-    const int wd = mimi_half(e) ? 2 : 1;  // activation elements per 32-bit word
-    BODY(sopro_fill2d_u32(w.e0, (int64_t)((1 + rowz) * chz / wd), B, (int)(chz / wd), 0u, s));
-    for (int si = 0; si < c.mimi_n_ratios; ++si) {
-      const size_t co = chz / 2, orow = rowz * c.mimi_ratios[si];
-      if (w.hraw[si]) BODY(sopro_fill2d_u32(w.hraw[si], (int64_t)((2 + orow) * co / wd), B, (int)(2 * co / wd), 0u, s));
-      if (w.hact[si]) BODY(sopro_fill2d_u32(w.hact[si], (int64_t)((2 + orow) * co / wd), B, (int)(2 * co / wd), 0u, s));
-      chz = co; rowz = orow;
+    const int wd = half ? 2 : 1;  // activation elements per 32-bit word
+    BODY(sopro_fill2d_u32(w.e0, (int64_t)(1 + N2) * lv[0].ch / wd, B, lv[0].ch / wd, 0u, s));
+    for (int si = 0; si < nl; ++si) {
+      const int64_t seg = (int64_t)(2 + lv[si].orow) * lv[si].co / wd;
+      if (w.hraw[si]) BODY(sopro_fill2d_u32(w.hraw[si], seg, B, 2 * lv[si].co / wd, 0u, s));
+      if (w.hact[si]) BODY(sopro_fill2d_u32(w.hact[si], seg, B, 2 * lv[si].co / wd, 0u, s));
     }
   }
   // ---- RVQ decode + output projections (HF:modeling_mimi.py:1128-1137)
@@ -1333,138 +1373,78 @@ static int mimi_decode_core(sopro_engine* e, void* workspace, const int32_t* tok
   const int attn_split = attn_exact ? 0 : ((c.precision == 1 && attn_one) ? 1 : 3);
   BODY(transformer_stack(e, s, "tr", w.X, PADX, xs, w.y, w.qkv, w.ao, w.hd, &w.sk, B, N2, past, sst, attn_split, w.lnst, sbt));
   static const bool three = SOPRO_DEV_ENV("SOPRO_SEANET_PASSES3") != nullptr;  // developer A/B: the fused kernels' three-pass form in bf16 mode too
-  const int sea_passes = (c.precision == 1 && !three) ? 1 : 3;
+  const int sea_passes = (c.precision == 1 && !three) ? 1 : 3;  // (the fused kernels' fp32-row entry points; the bf16-row ones take no `passes`)
   // ---- SEANet decoder (HF:931-961), activated-copy flow of sopro_amd.codec.MimiCodec._seanet_act
-  int ch = c.mimi_num_filters << c.mimi_n_ratios, rows = N2, pad_in = 1;
-  if (mimi_half(e)) {
-    // bf16 mode: the same flow with every activation of the decoder as bf16 rows in memory (strides below count bf16 elements):
-    // the first convolution reads the fp32 transformer stream and writes ELU(.) as bf16; every later contraction reads bf16
-    // rows (a_format 2: staged by plain copies) and writes bf16 rows (c_mode 6 raw / 7 activated / 8 both); the fused
-    // kernels of the two 24 kHz-side levels have bf16-row forms.  Accumulation, bias, ELU and the skip additions are fp32.
-    auto HP = [](float* p, size_t n) { return reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(p) + n); };
-    {
-      G g; g.sk = &w.sk; g.M = B * rows; g.N = ch; g.K = c.mimi_kernel * HS; g.lda = HS; g.bias = F(e, "sea.conv0.b"); g.rows_per_seg = rows; g.a_seg = xs;
-      g.c_seg = (int64_t)(1 + rows) * ch; g.ldc = ch; g.c_mode = 7;
-      BODY(gemm(s, w.X, WT(e, "sea.conv0.w"), nullptr, HP(w.e0, ch), g));
-    }
-    float* He16 = w.e0;
-    for (int si = 0; si < c.mimi_n_ratios; ++si) {
-      const int r = c.mimi_ratios[si], co = ch / 2, orow = rows * r, hid = co / c.mimi_compress;
-      const bool last = si == c.mimi_n_ratios - 1;
-      const std::string u = "sea.up" + std::to_string(si), rs = "sea.res" + std::to_string(si);
-      float* Ho = w.hraw[si];
-      G up; up.sk = &w.sk; up.M = B * rows; up.N = r * co; up.K = 2 * ch; up.lda = ch; up.bias = F(e, u + ".b"); up.rows_per_seg = rows; up.a_fmt = 2;
-      up.a_seg = (int64_t)(pad_in + rows) * ch; up.c_seg = (int64_t)(2 + orow) * co; up.ldc = (int64_t)r * co;
-      float* A = HP(He16, (size_t)(pad_in - 1) * ch);
-      if (last) {
-        SOPRO_CHECK_ARG(co == 64 && hid == 32, "the fused tail is written for a 64-channel last stage");
-        if (ch == 128 && r == 4 && seanet_fused(B, rows)) {  // the whole level in one kernel: h never reaches memory
-          if (!(parts & 2)) return 0;
-          sopro_prof_scope prof("seanet_uptail_kernel", 2.0 * B * rows * 256 * 256 + 2.0 * B * orow * (3 * 64 * 32 + 32 * 64 + 3 * 64), s);
-          return sopro_seanet_uptail_bf16(A, up.a_seg, F(e, u + ".w"), F(e, u + ".b"), F(e, rs + ".c1.w"), F(e, rs + ".c1.b"), F(e, rs + ".c2.w"),
-                                          F(e, rs + ".c2.b"), F(e, "sea.final.w"), c.mimi_final_bias, wav, orow, B, rows, s);
-        }
-        if (ch == 128 && r == 4) {
-          sopro_prof_scope prof((parts & 1) ? "seanet_up128_kernel" : nullptr, 2.0 * B * rows * 256 * 256, s);
-          BODY(sopro_seanet_up128_bf16(A, up.a_seg, F(e, u + ".w"), F(e, u + ".b"), HP(Ho, 2 * co), up.c_seg, B, rows, s));
-        } else {
-          up.c_mode = 6;
-          BODY(gemm(s, A, WT(e, u + ".w"), nullptr, HP(Ho, 2 * co), up));
-        }
-        if (!(parts & 2)) return 0;
-        sopro_prof_scope prof("seanet_tail_kernel", 2.0 * B * orow * (3 * 64 * 32 + 32 * 64 + 3 * 64), s);
-        return sopro_seanet_tail_bf16(Ho, (int64_t)(2 + orow) * co, F(e, rs + ".c1.w"), F(e, rs + ".c1.b"), F(e, rs + ".c2.w"), F(e, rs + ".c2.b"),
-                                      F(e, "sea.final.w"), c.mimi_final_bias, wav, orow, B, orow, s);
-      }
-      float* Hn = w.hact[si];
-      if (co == 128 && hid == 64) {
-        up.c_mode = 6;
-        BODY(gemm(s, A, WT(e, u + ".w"), nullptr, HP(Ho, 2 * co), up));
-        sopro_prof_scope prof((parts & 1) ? "seanet_res128_kernel" : nullptr, 2.0 * B * orow * (3 * 128 * 64 + 64 * 128), s);
-        BODY(sopro_seanet_res128_bf16(Ho, (int64_t)(2 + orow) * co, F(e, rs + ".c1.w"), F(e, rs + ".c1.b"), F(e, rs + ".c2.w"), F(e, rs + ".c2.b"), Hn,
-                                     (int64_t)(2 + orow) * co, B, orow, s));
-      } else {
-        up.c_mode = 8; up.C2 = HP(Hn, 2 * co); up.ldc2 = (int64_t)r * co; up.c2_seg = (int64_t)(2 + orow) * co;
-        BODY(gemm(s, A, WT(e, u + ".w"), nullptr, HP(Ho, 2 * co), up));
-        G c1; c1.sk = &w.sk; c1.M = B * orow; c1.N = hid; c1.K = 3 * co; c1.lda = co; c1.bias = F(e, rs + ".c1.b"); c1.rows_per_seg = orow; c1.a_fmt = 2;
-        c1.a_seg = (int64_t)(2 + orow) * co; c1.c_mode = 7;
-        BODY(gemm(s, Hn, WT(e, rs + ".c1.w"), nullptr, w.y1[si], c1));
-        G c2; c2.sk = &w.sk; c2.M = B * orow; c2.N = co; c2.K = hid; c2.bias = F(e, rs + ".c2.b"); c2.epi = SOPRO_EPI_RES; c2.R = HP(Ho, 2 * co); c2.rows_per_seg = orow;
-        c2.a_fmt = 2; c2.c_seg = (int64_t)(2 + orow) * co; c2.r_seg = (int64_t)(2 + orow) * co; c2.ldc = co; c2.ldr = co; c2.c_mode = 7;
-        BODY(gemm(s, w.y1[si], WT(e, rs + ".c2.w"), nullptr, HP(Hn, 2 * co), c2));
-      }
-      He16 = Hn; ch = co; rows = orow; pad_in = 2;
-    }
-    sopro_set_error("sopro_mimi_decode: the decoder has no last stage");
-    return -2;
-  }
-  // Round 6: the levels whose contractions have K >= 1024 hand their ACTIVATED tensors over in split form (every 32 channels =
-  // [32 hi | 32 lo] bf16: same bytes, lines and strides as fp32) - the producer's epilogue splits once (c_mode 1 / 2), and the long-K
-  // form of the contraction (gemm_8p.hip: both operands by LDS-DMA) takes them where there are tiles enough; the tile kernel reads the
-  // same tensors (a_format 1) when there are not (streaming chunks).  `in_split`: this level's input is in split form.
-  auto rows_of = [&](const std::string& k) { return WT(e, k).rows != nullptr; };
+  // Round 6: the levels whose contractions have K >= 1024 hand their ACTIVATED tensors over in split form - the producer's epilogue
+  // splits once, and the long-K form of the contraction (gemm_8p.hip: both operands by LDS-DMA) takes them where there are tiles
+  // enough; the tile kernel reads the same tensors when there are not (streaming chunks).  fp32 rows only: bf16 rows stay bf16 rows.
   static const bool no_8p = SOPRO_DEV_ENV("SOPRO_GEMM_8P") != nullptr && SOPRO_DEV_ENV("SOPRO_GEMM_8P")[0] == '0';  // developer A/B: the round-5 flow
-  bool in_split = !no_8p && rows_of("sea.up0.w");
+  auto split_if = [&](const std::string& k, bool ok) { return !half && !no_8p && WT(e, k).rows != nullptr && ok ? ACT_SPLIT : rowf; };
+  ActFmt fin = split_if("sea.up0.w", true);  // the format of the level's (activated) input
   {  // first conv k = 7 -> ELU; one zero row in front = x[t-1] of the transposed conv
-    G g; g.sk = &w.sk; g.M = B * rows; g.N = ch; g.K = c.mimi_kernel * HS; g.lda = HS; g.bias = F(e, "sea.conv0.b"); g.rows_per_seg = rows; g.a_seg = xs;
-    g.c_seg = (int64_t)(1 + rows) * ch; g.ldc = ch; g.c_mode = in_split ? 1 : 3;
-    BODY(gemm(s, w.X, WT(e, "sea.conv0.w"), nullptr, w.e0 + ch, g));
+    const int ch = lv[0].ch;
+    G g; g.sk = &w.sk; g.M = B * N2; g.N = ch; g.K = c.mimi_kernel * HS; g.lda = HS; g.bias = F(e, "sea.conv0.b"); g.rows_per_seg = N2; g.a_seg = xs;
+    g.c_seg = (int64_t)(1 + N2) * ch; g.ldc = ch; g.c_mode = act_c_mode(OUT_ACT, fin);
+    BODY(gemm(s, w.X, WT(e, "sea.conv0.w"), nullptr, act_at(w.e0, rowf, ch), g));
   }
-  const float* He = w.e0;
-  for (int si = 0; si < c.mimi_n_ratios; ++si) {
-    const int r = c.mimi_ratios[si], co = ch / 2, orow = rows * r, hid = co / c.mimi_compress;
-    const bool last = si == c.mimi_n_ratios - 1;
+  float* He = w.e0;
+  for (int si = 0; si < nl; ++si) {
+    const SeaLevel& l = lv[si];
+    const int ch = l.ch, co = l.co, rows = l.rows, orow = l.orow, r = l.r, hid = l.hid, pad_in = si ? 2 : 1;
+    const int64_t oseg = (int64_t)(2 + orow) * co;  // a segment of the level's buffers: two zero rows, then its orow rows
     const std::string u = "sea.up" + std::to_string(si), rs = "sea.res" + std::to_string(si);
-    float* Ho = w.hraw[si];
-    G up; up.sk = &w.sk; up.M = B * rows; up.N = r * co; up.K = 2 * ch; up.lda = ch; up.bias = F(e, u + ".b"); up.rows_per_seg = rows;
-    up.a_seg = (int64_t)(pad_in + rows) * ch; up.c_seg = (int64_t)(2 + orow) * co; up.ldc = (int64_t)r * co;
-    up.a_fmt = in_split ? 1 : 0;
-    const float* A = He + (size_t)(pad_in - 1) * ch;
-    if (last) {
+    const float *wu = F(e, u + ".w"), *bu = F(e, u + ".b"), *w1 = F(e, rs + ".c1.w"), *b1 = F(e, rs + ".c1.b"), *w2 = F(e, rs + ".c2.w"), *b2 = F(e, rs + ".c2.b");
+    float *Ho = w.hraw[si], *Hn = w.hact[si];
+    float* raw = Ho ? act_at(Ho, rowf, 2 * co) : nullptr;  // the level's raw rows, behind the two zero rows (none: the fused last level)
+    G up; up.sk = &w.sk; up.M = B * rows; up.N = r * co; up.K = 2 * ch; up.lda = ch; up.bias = bu; up.rows_per_seg = rows;
+    up.a_seg = (int64_t)(pad_in + rows) * ch; up.c_seg = oseg; up.ldc = (int64_t)r * co;
+    up.a_fmt = fin; up.c_mode = act_c_mode(OUT_RAW, rowf);
+    const float* A = act_at(He, rowf, (size_t)(pad_in - 1) * ch);
+    if (l.last) {
       SOPRO_CHECK_ARG(co == 64 && hid == 32, "the fused tail is written for a 64-channel last stage");
-      if (ch == 128 && r == 4 && seanet_fused(B, rows)) {  // the whole level in one kernel: h never reaches memory
+      const float* wf = F(e, "sea.final.w");
+      if (l.fused) {  // the whole level in one kernel: h never reaches memory
         if (!(parts & 2)) return 0;
         sopro_prof_scope prof("seanet_uptail_kernel", 2.0 * B * rows * 256 * 256 + 2.0 * B * orow * (3 * 64 * 32 + 32 * 64 + 3 * 64), s);
-        return sopro_seanet_uptail_f32(A, up.a_seg, F(e, u + ".w"), F(e, u + ".b"), F(e, rs + ".c1.w"), F(e, rs + ".c1.b"), F(e, rs + ".c2.w"),
-                                       F(e, rs + ".c2.b"), F(e, "sea.final.w"), c.mimi_final_bias, wav, orow, B, rows, sea_passes, s);
+        return half ? sopro_seanet_uptail_bf16(A, up.a_seg, wu, bu, w1, b1, w2, b2, wf, c.mimi_final_bias, wav, orow, B, rows, s)
+                    : sopro_seanet_uptail_f32(A, up.a_seg, wu, bu, w1, b1, w2, b2, wf, c.mimi_final_bias, wav, orow, B, rows, sea_passes, s);
       }
       if (ch == 128 && r == 4) {  // weight-stationary form of the K = 256, N = 256 contraction (same results)
         sopro_prof_scope prof((parts & 1) ? "seanet_up128_kernel" : nullptr, 2.0 * B * rows * 256 * 256, s);
-        BODY(sopro_seanet_up128_f32(A, up.a_seg, F(e, u + ".w"), F(e, u + ".b"), Ho + 2 * co, up.c_seg, B, rows, c.precision == 1 ? 1 : 3, s));
+        // (as it always was: this entry point gets its passes from the precision alone, SOPRO_SEANET_PASSES3 does not reach it)
+        BODY(half ? sopro_seanet_up128_bf16(A, up.a_seg, wu, bu, raw, oseg, B, rows, s)
+                  : sopro_seanet_up128_f32(A, up.a_seg, wu, bu, raw, oseg, B, rows, c.precision == 1 ? 1 : 3, s));
       } else {
-        BODY(gemm(s, A, WT(e, u + ".w"), nullptr, Ho + 2 * co, up));
+        BODY(gemm(s, A, WT(e, u + ".w"), nullptr, raw, up));
       }
       // last residual block (k=3 conv 64->32, k=1 conv 32->64) + final k=3 conv 64->1 per output sample
       if (!(parts & 2)) return 0;
       sopro_prof_scope prof("seanet_tail_kernel", 2.0 * B * orow * (3 * 64 * 32 + 32 * 64 + 3 * 64), s);
-      return sopro_seanet_tail_p_f32(Ho, (int64_t)(2 + orow) * co, F(e, rs + ".c1.w"), F(e, rs + ".c1.b"), F(e, rs + ".c2.w"), F(e, rs + ".c2.b"),
-                                     F(e, "sea.final.w"), c.mimi_final_bias, wav, orow, B, orow, sea_passes, s);
+      return half ? sopro_seanet_tail_bf16(Ho, oseg, w1, b1, w2, b2, wf, c.mimi_final_bias, wav, orow, B, orow, s)
+                  : sopro_seanet_tail_p_f32(Ho, oseg, w1, b1, w2, b2, wf, c.mimi_final_bias, wav, orow, B, orow, sea_passes, s);
     }
-    float* Hn = w.hact[si];
-    if (co == 128 && hid == 64) {
-      BODY(gemm(s, A, WT(e, u + ".w"), nullptr, Ho + 2 * co, up));
+    if (l.res128) {
+      BODY(gemm(s, A, WT(e, u + ".w"), nullptr, raw, up));
       sopro_prof_scope prof((parts & 1) ? "seanet_res128_kernel" : nullptr, 2.0 * B * orow * (3 * 128 * 64 + 64 * 128), s);
-      BODY(sopro_seanet_res128_p_f32(Ho, (int64_t)(2 + orow) * co, F(e, rs + ".c1.w"), F(e, rs + ".c1.b"), F(e, rs + ".c2.w"), F(e, rs + ".c2.b"), Hn,
-                                    (int64_t)(2 + orow) * co, B, orow, sea_passes, s));
-      in_split = false;
+      BODY(half ? sopro_seanet_res128_bf16(Ho, oseg, w1, b1, w2, b2, Hn, oseg, B, orow, s)
+                : sopro_seanet_res128_p_f32(Ho, oseg, w1, b1, w2, b2, Hn, oseg, B, orow, sea_passes, s));
+      fin = rowf;
     } else {
       // the block's tensors in split form when its k = 3 convolution has the long-K operand; its output (only ever read through ELU,
-      // by the next level) goes on in split form with them
-      // (never into the last level: its fused kernels read fp32 rows)
-      const bool mid_split = !no_8p && rows_of(rs + ".c1.w") && (co & 31) == 0 && (hid & 31) == 0 && si + 1 < c.mimi_n_ratios - 1;
-      up.c_mode = mid_split ? 2 : 4; up.C2 = Hn + 2 * co; up.ldc2 = (int64_t)r * co; up.c2_seg = (int64_t)(2 + orow) * co;
-      BODY(gemm(s, A, WT(e, u + ".w"), nullptr, Ho + 2 * co, up));
+      // by the next level) goes on in split form with them (never into the last level: its fused kernels read whole rows)
+      const ActFmt fmid = split_if(rs + ".c1.w", (co & 31) == 0 && (hid & 31) == 0 && si + 1 < nl - 1);
+      up.c_mode = act_c_mode(OUT_RAW_ACT, fmid); up.C2 = act_at(Hn, rowf, 2 * co); up.ldc2 = (int64_t)r * co; up.c2_seg = oseg;
+      BODY(gemm(s, A, WT(e, u + ".w"), nullptr, raw, up));
       // residual block: x + Conv1d(k=1)(ELU(Conv1d(k=3)(ELU(x)))); its output is only ever read through ELU
-      G c1; c1.sk = &w.sk; c1.M = B * orow; c1.N = hid; c1.K = 3 * co; c1.lda = co; c1.bias = F(e, rs + ".c1.b"); c1.rows_per_seg = orow;
-      c1.a_seg = (int64_t)(2 + orow) * co; c1.c_mode = mid_split ? 1 : 3; c1.a_fmt = mid_split ? 1 : 0;
+      G c1; c1.sk = &w.sk; c1.M = B * orow; c1.N = hid; c1.K = 3 * co; c1.lda = co; c1.bias = b1; c1.rows_per_seg = orow;
+      c1.a_seg = oseg; c1.a_fmt = fmid; c1.c_mode = act_c_mode(OUT_ACT, fmid);
       BODY(gemm(s, Hn, WT(e, rs + ".c1.w"), nullptr, w.y1[si], c1));
-      G c2; c2.sk = &w.sk; c2.M = B * orow; c2.N = co; c2.K = hid; c2.bias = F(e, rs + ".c2.b"); c2.epi = SOPRO_EPI_RES; c2.R = Ho + 2 * co; c2.rows_per_seg = orow;
-      c2.c_seg = (int64_t)(2 + orow) * co; c2.r_seg = (int64_t)(2 + orow) * co; c2.ldc = co; c2.ldr = co; c2.c_mode = mid_split ? 1 : 3;
-      c2.a_fmt = mid_split ? 1 : 0;
-      BODY(gemm(s, w.y1[si], WT(e, rs + ".c2.w"), nullptr, Hn + 2 * co, c2));
-      in_split = mid_split;
+      G c2; c2.sk = &w.sk; c2.M = B * orow; c2.N = co; c2.K = hid; c2.bias = b2; c2.epi = SOPRO_EPI_RES; c2.R = raw; c2.rows_per_seg = orow;
+      c2.c_seg = oseg; c2.r_seg = oseg; c2.ldc = co; c2.ldr = co; c2.a_fmt = fmid; c2.c_mode = act_c_mode(OUT_ACT, fmid);
+      BODY(gemm(s, w.y1[si], WT(e, rs + ".c2.w"), nullptr, act_at(Hn, rowf, 2 * co), c2));
+      fin = fmid;
     }
-    He = Hn; ch = co; rows = orow; pad_in = 2;
+    He = Hn;
   }
   sopro_set_error("sopro_mimi_decode: the decoder has no last stage");
   return -2;
@@ -1627,21 +1607,20 @@ int sopro_mimi_stream_init(const sopro_engine* e, sopro_mimi_stream_state* st, v
   return 0;
 }
 
-int sopro_mimi_stream_trim(sopro_mimi_stream_state* st, int32_t n) {
-  SOPRO_CHECK_ARG(st && n >= 0, "bad arguments");
-  if (st->kv_len == 0 || n == 0) return 0;
+// The cache bookkeeping of the single stream and of the batch (both structs are public and keep their layouts: the same field names).
+extern "C++" {  // (a template cannot have C linkage)
+// legacy trim: drop the last n cached rows of every layer; the rebuilt cache is made of plain layers that never evict
+template <class St>
+static void stream_trim(St* st, int n) {
+  if (st->kv_len == 0 || n == 0) return;
   st->kv_len = st->kv_len > n ? st->kv_len - n : 0;
   st->pos = st->kv_len;  // positions continue from the trimmed length: the rebuilt cache reports its own length
   st->evict = 0;
-  return 0;
 }
-
-int sopro_mimi_decode_stream(sopro_engine* e, void* workspace, sopro_mimi_stream_state* st, const int32_t* tokens, int32_t T, float* wav,
-                             void* stream) {
-  SOPRO_CHECK_ARG(st != nullptr, "state is NULL");
-  const int n = 2 * T, Tk = st->kv_len + n;
-  const int rc = mimi_decode_core(e, workspace, tokens, 1, T, wav, stream, st);
-  if (rc != 0) return rc;
+// after a call of n rows: what transformer_stack left in the cache (evicting policy: window - 1 rows, in the other half)
+template <class St>
+static void stream_advance(const sopro_engine* e, St* st, int n) {
+  const int Tk = st->kv_len + n;
   if (st->evict && Tk > e->c.mimi_window - 1) {
     st->kv_len = e->c.mimi_window - 1;
     st->half ^= 1;
@@ -1649,6 +1628,20 @@ int sopro_mimi_decode_stream(sopro_engine* e, void* workspace, sopro_mimi_stream
     st->kv_len = Tk;
   }
   st->pos += n;
+}
+}  // extern "C++"
+
+int sopro_mimi_stream_trim(sopro_mimi_stream_state* st, int32_t n) {
+  SOPRO_CHECK_ARG(st && n >= 0, "bad arguments");
+  stream_trim(st, n);
+  return 0;
+}
+
+int sopro_mimi_decode_stream(sopro_engine* e, void* workspace, sopro_mimi_stream_state* st, const int32_t* tokens, int32_t T, float* wav,
+                             void* stream) {
+  SOPRO_CHECK_ARG(st != nullptr, "state is NULL");
+  STG(mimi_decode_core(e, workspace, tokens, 1, T, wav, stream, st));
+  stream_advance(e, st, 2 * T);
   return 0;
 }
 
@@ -1672,10 +1665,7 @@ int sopro_mimi_stream_batch_init(const sopro_engine* e, sopro_mimi_stream_batch*
 
 int sopro_mimi_stream_batch_trim(sopro_mimi_stream_batch* st, int32_t n) {
   SOPRO_CHECK_ARG(st && n >= 0, "bad arguments");
-  if (st->kv_len == 0 || n == 0) return 0;
-  st->kv_len = st->kv_len > n ? st->kv_len - n : 0;
-  st->pos = st->kv_len;
-  st->evict = 0;
+  stream_trim(st, n);
   return 0;
 }
 
@@ -1704,16 +1694,8 @@ int sopro_mimi_decode_stream_batch(sopro_engine* e, void* workspace, sopro_mimi_
   SOPRO_CHECK_ARG(e && st->rows >= 1 && st->rows <= st->rows_cap && T > 0, "bad arguments");
   // the workspace of sopro_mimi_workspace_bytes(e, rows, T) holds one chunk of rows: the call decodes all rows at once
   SOPRO_CHECK_ARG(st->rows <= sopro_mimi_chunk_rows(st->rows, T), "rows x T exceeds one decode chunk (sopro_mimi_chunk_rows)");
-  const int n = 2 * T, Tk = st->kv_len + n;
-  const int rc = mimi_decode_core(e, workspace, tokens, st->rows, T, wav, stream, nullptr, 3, st);
-  if (rc != 0) return rc;
-  if (st->evict && Tk > e->c.mimi_window - 1) {
-    st->kv_len = e->c.mimi_window - 1;
-    st->half ^= 1;
-  } else {
-    st->kv_len = Tk;
-  }
-  st->pos += n;
+  STG(mimi_decode_core(e, workspace, tokens, st->rows, T, wav, stream, nullptr, 3, st));
+  stream_advance(e, st, 2 * T);
   return 0;
 }
 

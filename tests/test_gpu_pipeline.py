@@ -394,15 +394,50 @@ def test_full_size_properties_32x200(tts, cfg, sopro_np, mimi_np):
     assert _err(wav[:, : 50 * 1920], pre) < 1e-4 * float(wav.abs().max()), "decoder is not causal in the frame index"
 
 
-def test_decode_batch_in_row_chunks_equals_one_call(tts, monkeypatch):
+def test_decode_batch_in_row_chunks_equals_one_call(tts):
     """Round 4: large batches are decoded in row chunks (a 64 x 400 decode in one call is slower than two 32 x 400 calls);
-    every utterance's samples must not depend on the chunking (rows are independent; no few-row split-K at these sizes)."""
+    every utterance's samples must not depend on the chunking.  33 x 400 frames are 13200 cells, above the default 12800 of
+    SOPRO_MIMI_CHUNK_CELLS (read once per process: no test can change it), so the call runs as 17 + 16 rows: bit for bit the two
+    calls of those row counts (the same launches), and a second call replays the recorded sequences."""
+    from sopro_amd import hip
+
+    assert int(hip.load().sopro_mimi_chunk_rows(33, 400)) == 17  # (or the call below is one chunk and this test compares nothing)
     rng = np.random.default_rng(91)
-    codes = torch.from_numpy(rng.integers(0, 2048, size=(5, 300, 32)))
-    monkeypatch.setenv("SOPRO_MIMI_CHUNK_CELLS", "100000")
-    one = tts.codec.decode_batch(codes)
-    monkeypatch.setenv("SOPRO_MIMI_CHUNK_CELLS", "600")  # 2 rows per chunk: 2 + 2 + 1
+    codes = torch.from_numpy(rng.integers(0, 2048, size=(33, 400, 32)))
     chunked = tts.codec.decode_batch(codes)
-    again = tts.codec.decode_batch(codes)  # (the chunk shapes replay their recorded sequences)
-    assert tuple(one.shape) == (5, 300 * 1920) and torch.equal(chunked, again)
-    assert float((one - chunked).abs().max()) <= 2e-6 * float(one.abs().max())  # (another tile walk for another row count: round-off class)
+    assert tuple(chunked.shape) == (33, 400 * 1920) and bool(torch.isfinite(chunked).all())
+    assert torch.equal(chunked, torch.cat([tts.codec.decode_batch(codes[:17]), tts.codec.decode_batch(codes[17:])]))
+    assert torch.equal(chunked, tts.codec.decode_batch(codes))
+
+
+def test_decode_fused_last_level_equals_the_two_kernel_form(tts, mimi_np):
+    """The last SEANet level runs as ONE kernel from 524288 input rows per call on (B * 480 * T), as two below: 3 x 365 frames
+    (525600 rows) take the fused form, each row alone (175200) the two-kernel form; neither has the few-row split-K scratch
+    (B * 2T > 512).  fp32: per row within tests/test_gpu_uptail.py's bound for the fused level against the two kernels (that
+    level's output is the waveform) plus test_decode_batch_in_row_chunks_equals_one_call's former bound for another row count's
+    tile walk.  3 x 364 frames (524160 rows) sit one step below the threshold: both sides of it run through the workspace carve.
+    bf16 mode: the two forms round differently (the 64-channel activation is stored as bf16 rows in one and stays on the CU in
+    the other), so each is measured against the fp32 decode of the same codes, and the fused form may not be worse than the
+    two-kernel form by more than a quarter (measured on the MI355X: fused 5.41e-02, two kernels 5.82e-02 at a peak of 6.83)."""
+    from sopro_amd.codec import MimiCodec
+    from sopro_amd.config import MimiDecoderConfig
+
+    rng = np.random.default_rng(365)
+    codes = torch.from_numpy(rng.integers(0, 2048, size=(3, 365, 32)))
+
+    def both_forms(codec):
+        return codec.decode_batch(codes), torch.cat([codec.decode_batch(codes[b:b + 1]) for b in range(3)])
+
+    fused, two = both_forms(tts.codec)
+    assert tuple(fused.shape) == tuple(two.shape) == (3, 365 * 1920) and bool(torch.isfinite(fused).all()) and bool(torch.isfinite(two).all())
+    for b in range(3):
+        peak = float(two[b].abs().max())
+        assert _err(fused[b], two[b]) <= 5e-6 * (peak + 1.0) + 2e-6 * peak, b
+    below = tts.codec.decode_batch(codes[:, :364])
+    assert tuple(below.shape) == (3, 364 * 1920) and bool(torch.isfinite(below).all())
+    c16 = MimiCodec(mimi_np, MimiDecoderConfig(num_quantizers=32), "cuda:0", precision="bf16")
+    fused16, two16 = both_forms(c16)
+    assert tuple(fused16.shape) == (3, 365 * 1920) and bool(torch.isfinite(fused16).all()) and bool(torch.isfinite(two16).all())
+    e_fused, e_two = _err(fused16, fused), _err(two16, fused)
+    print(f"\nbf16 mode, 3 x 365 frames against the fp32 decode: fused last level {e_fused:.3e}, two kernels {e_two:.3e} (peak {float(fused.abs().max()):.3e})")
+    assert e_fused <= 1.25 * e_two

@@ -923,6 +923,24 @@ def copy_u32(dst: torch.Tensor, src: torch.Tensor) -> None:
     _check(load().sopro_copy2d_u32(dst.data_ptr(), n, src.data_ptr(), n, 1, n, _stream()), "sopro_copy2d_u32")
 
 
+def fill2d(p: torch.Tensor, value: int, *, rows: int, width: int, pitch: int, p_off: int = 0) -> None:
+    """rows x width 32-bit words, ``pitch`` words apart, <- value (sopro_fill2d_u32); ``p_off``: word offset into ``p``."""
+    _check(load().sopro_fill2d_u32(ptr(p, p.dtype) + 4 * p_off, pitch, rows, width, int(value) & 0xFFFFFFFF, _stream()), "sopro_fill2d_u32")
+
+
+def copy2d(dst: torch.Tensor, src: torch.Tensor, *, rows: int, width: int, dpitch: int, spitch: int, d_off: int = 0, s_off: int = 0) -> None:
+    """rows x width 32-bit words between two pitched layouts (sopro_copy2d_u32); offsets in words."""
+    _check(load().sopro_copy2d_u32(ptr(dst, dst.dtype) + 4 * d_off, dpitch, ptr(src, src.dtype) + 4 * s_off, spitch, rows, width, _stream()),
+           "sopro_copy2d_u32")
+
+
+def nar_seed(tokens: torch.Tensor, cb0: torch.Tensor, *, Q: int, B: int, T: int, vmax: int, cb0_bstride: Optional[int] = None,
+             cb0_off: int = 0) -> None:
+    """Column 0 of the token matrix [B T, Q] <- codebook 0 of the AR history, clamped to [0, vmax] (sopro_nar_seed_i32)."""
+    _check(load().sopro_nar_seed_i32(ptr(tokens, torch.int32), Q, ptr(cb0, torch.int32) + 4 * cb0_off, T if cb0_bstride is None else cb0_bstride,
+                                     B, T, vmax, _stream()), "sopro_nar_seed_i32")
+
+
 def set_lds_floor(nbytes: int) -> None:
     """Minimum dynamic-LDS request of the split-bf16 GEMM launches (> 80 KiB: one workgroup per CU); see sopro_set_lds_floor."""
     _check(load().sopro_set_lds_floor(int(nbytes)), "sopro_set_lds_floor")

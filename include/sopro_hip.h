@@ -133,7 +133,9 @@ typedef struct sopro_gemm_split_ext {
                      * 3: ELU(C) as fp32 to C; 4: fp32 to C and ELU(C) as fp32 to C2; 5: arg-max partials (see sopro_argmax_partials_i32);
                      * sopro_gemm_bf16x1 only, epilogue NONE or RES: 6: C as bf16 rows; 7: ELU(C) as bf16 rows to C; 8: C as bf16 rows to C
                      * AND ELU(C) as bf16 rows to C2 - C / C2 / R (the skip operand of EPI_RES) then point at bf16 elements and
-                     * ldc / ldc2 / ldr and the segment strides count bf16 elements (multiples of 4, 8-byte aligned rows) */
+                     * ldc / ldc2 / ldr and the segment strides count bf16 elements (multiples of 4, 8-byte aligned rows); N % 4 == 0 is
+                     * required (a call with another N is refused): a thread handles four columns at a time and reads scale[n .. n + 3]
+                     * after testing n < N alone, so `scale` needs no more than its N entries */
   float* C2; int64_t ldc2; int64_t c2_seg_stride; /* c_mode 2 / 4; strides in 4-byte units like ldc / c_seg_stride */
   /* Split-K for problems with too few output tiles to fill the chip (a few rows: streaming chunks, batch 1): `ksplit`
    * workgroups share a tile, each stores its raw accumulators into `ws`, the last to take the tile's ticket adds them in
@@ -179,7 +181,7 @@ int sopro_gemm_bf16x3(const sopro_gemm_args* a, const void* packed_w, const sopr
  * main loop).  For the SEANet decoder's K >= 1024 contractions (HF:modeling_mimi.py:350-405 MimiConvTranspose1d as a row-window
  * contraction; :408-447 the first residual block's k = 3 convolution): 1.3-1.4x the tile kernel there.  A must be split-form rows
  * (a_format 1: what a producer's c_mode 1 / 2 writes), the weight comes from sopro_pack_w_rows_bf16: [N][K / 32][32 hi | 32 lo] bf16,
- * sopro_packed_w_rows_bytes(N, K) bytes, 128-byte aligned.  N % 256 == 0, K % 32 == 0; epilogue NONE (+ bias); c_mode 0 / 1 / 2 / 4; no
+ * sopro_packed_w_rows_bytes(N, K) bytes, 128-byte aligned.  N % 256 == 0, K % 32 == 0 (from K = 32, one K-tile, up); epilogue NONE (+ bias); c_mode 0 / 1 / 2 / 4; no
  * split-K.  sopro_gemm_8p_takes: 1 when a call with these (args, ext) is one this form takes AND has enough tiles to pay (what the
  * stage sequences ask before they route a contraction here). */
 int64_t sopro_packed_w_rows_bytes(int32_t N, int32_t K);

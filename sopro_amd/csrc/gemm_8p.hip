@@ -273,7 +273,9 @@ extern "C" int sopro_gemm_bf16x3_8p(const sopro_gemm_args* a, const void* w_rows
   if (g.c_seg_stride == 0) g.c_seg_stride = (int64_t)g.rows_per_seg * g.ldc;
   if (ext.c2_seg_stride == 0) ext.c2_seg_stride = (int64_t)g.rows_per_seg * ext.ldc2;
   SOPRO_CHECK_ARG(g.M > 0 && g.N > 0 && g.K > 0 && g.rows_per_seg > 0, "M, N, K, rows_per_seg must be positive");
-  SOPRO_CHECK_ARG((g.N % P_BN) == 0 && (g.K & 31) == 0 && g.K >= 64, "the long-K form takes N % 256 == 0, K % 32 == 0, K >= 64");
+  // (K = 32, one K-tile: the requests for tiles 1 and 2 are clamped onto tile 0 like the ones behind the last tile of any K - they
+  // land in a buffer nobody reads again, or rewrite a half-tile with the bytes it holds; barriers and counted waits are per K-tile)
+  SOPRO_CHECK_ARG((g.N % P_BN) == 0 && (g.K & 31) == 0, "the long-K form takes N % 256 == 0, K % 32 == 0");
   SOPRO_CHECK_ARG(ext.a_format == 1 && g.prologue == SOPRO_PRO_NONE, "A must be split-form rows (a_format 1, no prologue)");
   SOPRO_CHECK_ARG(g.epilogue == SOPRO_EPI_NONE && !ext.rms_norm && !ext.ln_stats && !ext.ln_stats_out && ext.ksplit <= 1,
                   "epilogue NONE, no fused norm, no split-K");

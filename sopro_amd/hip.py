@@ -428,10 +428,12 @@ def gemm(A: torch.Tensor, W, Cout: torch.Tensor, *, M: int, N: int, K: int, lda:
          C2: Optional[torch.Tensor] = None, ldc2: Optional[int] = None, c2_seg_stride: int = 0,
          c2_off: int = 0, rms_eps: float = 0.0, range_events: Optional[torch.Tensor] = None, rope: Optional[tuple] = None,
          ln_stats: Optional[torch.Tensor] = None, ln_eps: float = 0.0, ln_stats_out: Optional[torch.Tensor] = None,
-         long_k: Optional[bool] = None) -> None:
+         long_k: Optional[bool] = None, ksplit: Optional[int] = None, group_m: Optional[int] = None) -> None:
     """C = epi(pro(A) @ W^T + bias); offsets are in elements from the tensors' first element.  With a ``PackedW`` weight the
     contraction runs on the split-bf16 path, where ``a_split`` says A is in split form and ``c_mode`` 1 / 2 writes
-    ELU(C) in split form (to C, or to C2 next to the fp32 C): see sopro_gemm_split_ext in include/sopro_hip.h."""
+    ELU(C) in split form (to C, or to C2 next to the fp32 C): see sopro_gemm_split_ext in include/sopro_hip.h.
+    ``ksplit`` (packed weights): an explicit K-slice count instead of ``_auto_ksplit``'s, on the same per-stream scratch
+    (``_splitk_buffers``); ``group_m``: sopro_gemm_split_ext.group_m (None = the library's default tile walk)."""
     n_out = N // 2 if epilogue == EPI_GLU else N
     g = GemmArgs()
     a16 = A.dtype == torch.bfloat16  # bf16 rows (a_format 2 of sopro_gemm_bf16x1): offsets / strides count bf16 elements
@@ -472,8 +474,18 @@ def gemm(A: torch.Tensor, W, Cout: torch.Tensor, *, M: int, N: int, K: int, lda:
             if W.pieces == 2 and not W.f16:
                 raise SoproHipError("fused RMSNorm is a six-pass (pieces = 3), f16 three-pass or one-pass (pieces = 1) feature")
             x.rms_norm, x.rms_eps = 1, float(rms_eps)
-        ks = _auto_ksplit(M, N, K, 3 if W.f16 else W.pieces, epilogue) if (dbg is None and _splitk_enabled and rms_eps <= 0.0) else 1
-        if ks > 1:
+        if group_m is not None:
+            x.group_m = int(group_m)
+        if ksplit is not None:
+            ks = int(ksplit)
+            # an early refusal only: what even the smallest tile (64 x 64) would need.  The library's own check, against the
+            # tile it really launches, is what keeps a launch inside the workspace and the tickets.
+            t64 = -(-M // 64) * -(-N // 64)
+            if ks > 1 and (ks * t64 * 64 * 64 * 4 > _SPLITK_WS_BYTES or t64 > _SPLITK_TICKETS):
+                raise SoproHipError(f"ksplit={ks}: {M} x {N} does not fit the split-K workspace / tickets of a stream")
+        else:
+            ks = _auto_ksplit(M, N, K, 3 if W.f16 else W.pieces, epilogue) if (dbg is None and _splitk_enabled and rms_eps <= 0.0) else 1
+        if ks > 1 or ksplit is not None:
             ws, tk = _splitk_buffers()
             x.ksplit, x.n_tickets, x.ws, x.ws_bytes, x.tickets = ks, int(tk.numel()), ptr(ws), int(ws.numel()) * 4, ptr(tk, torch.int32)
     if (a16 or c16) and not (packed and W.pieces == 1 and not W.f16):
@@ -516,6 +528,8 @@ def gemm(A: torch.Tensor, W, Cout: torch.Tensor, *, M: int, N: int, K: int, lda:
             _check(load().sopro_gemm_bf16x3(C.byref(g), ptr(W.data, torch.int32), C.byref(x), _stream()), "sopro_gemm_bf16x3")
     elif a_split or c_mode:
         raise SoproHipError("split-plane operands need a PackedW weight (the fp32 kernel reads and writes fp32 rows)")
+    elif ksplit is not None or group_m is not None:
+        raise SoproHipError("ksplit / group_m belong to the packed-weight paths (sopro_gemm_split_ext)")
     else:
         _check(load().sopro_gemm_f32(C.byref(g), _stream()), "sopro_gemm_f32")
     if e0 is not None:

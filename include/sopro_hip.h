@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SOPRO_ABI_VERSION 42
+#define SOPRO_ABI_VERSION 43
 
 /* ---- error handling / introspection ------------------------------------------------ */
 const char* sopro_last_error(void);
@@ -226,6 +226,11 @@ int sopro_gemm_f16x3(const sopro_gemm_args* a, const void* packed_w, const sopro
 int64_t sopro_packed_w_bytes(int32_t N, int32_t K, int32_t pieces);
 int sopro_gemm_bf16_set_tile_override(int cfg); /* developer probe: 0 = by shape, 1: 128x128, 2: 256x128, 4: 128x64, 5: 64x64, 7: 128x128 on eight waves (bf16x3 only) */
 int sopro_gemm_set_group_m(int g);              /* default tile-walk group of the split-bf16 contractions (see group_m) */
+/* Host only (no device needed): the `ksplit` worth offering a contraction of M x N x K on the tile its family launches by default -
+ * pieces 1 / 2 / 3 as in sopro_pack_w_bf16, f16 != 0 for sopro_gemm_f16x3 - given the caller's workspace bytes and ticket count; 1 = do
+ * not split (enough tiles, K < 1024, or SOPRO_NO_SPLITK=1 in the environment).  Whether a call may split at all (no fused RMSNorm, no
+ * clock-stamp probe, ...) is the caller's to decide before it asks. */
+int sopro_gemm_auto_ksplit(int32_t M, int32_t N, int32_t K, int32_t pieces, int32_t f16, int32_t epilogue, int64_t ws_bytes, int32_t n_tickets);
 
 /* Batch-of-at-most-a-few-dozen-rows contraction for the autoregressive step
  * (src/sopro/nn/generator.py:98-130): Y[b, n] = epi( rs[b] * sum_k Xin[b, k] * W[n, k] + bias[n] ),

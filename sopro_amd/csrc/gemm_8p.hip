@@ -26,6 +26,7 @@
 // the MFMAs instead of next to the fragment reads +5 %, without barriers -8 %.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -269,10 +270,7 @@ extern "C" int sopro_gemm_bf16x3_8p(const sopro_gemm_args* a, const void* w_rows
   SOPRO_CHECK_ARG(a != nullptr && x != nullptr && w_rows != nullptr, "args / ext / w_rows is NULL");
   sopro_gemm_args g = *a;
   sopro_gemm_split_ext ext = *x;
-  if (g.a_seg_stride == 0) g.a_seg_stride = (int64_t)g.rows_per_seg * g.lda;
-  if (g.c_seg_stride == 0) g.c_seg_stride = (int64_t)g.rows_per_seg * g.ldc;
-  if (ext.c2_seg_stride == 0) ext.c2_seg_stride = (int64_t)g.rows_per_seg * ext.ldc2;
-  SOPRO_CHECK_ARG(g.M > 0 && g.N > 0 && g.K > 0 && g.rows_per_seg > 0, "M, N, K, rows_per_seg must be positive");
+  if (int rc = gemm_check_basic(__func__, g, &ext, w_rows, GEMM_SPLIT_ROWS)) return rc;
   // (K = 32, one K-tile: the requests for tiles 1 and 2 are clamped onto tile 0 like the ones behind the last tile of any K - they
   // land in a buffer nobody reads again, or rewrite a half-tile with the bytes it holds; barriers and counted waits are per K-tile)
   SOPRO_CHECK_ARG((g.N % P_BN) == 0 && (g.K & 31) == 0, "the long-K form takes N % 256 == 0, K % 32 == 0");
@@ -283,17 +281,7 @@ extern "C" int sopro_gemm_bf16x3_8p(const sopro_gemm_args* a, const void* w_rows
                   "split-form A: 128-byte aligned base, lda / a_seg_stride multiples of 32");
   SOPRO_CHECK_ARG((reinterpret_cast<uintptr_t>(w_rows) & 127u) == 0, "w_rows must be 128-byte aligned (sopro_pack_w_rows_bf16)");
   SOPRO_CHECK_ARG(ext.c_mode == 0 || ext.c_mode == 1 || ext.c_mode == 2 || ext.c_mode == 4, "c_mode must be 0, 1, 2 or 4");
-  if (ext.c_mode != 0) {
-    const bool second = ext.c_mode == 2 || ext.c_mode == 4;
-    float* d = second ? ext.C2 : g.C;
-    const int64_t ldd = second ? ext.ldc2 : g.ldc, dseg = second ? ext.c2_seg_stride : g.c_seg_stride;
-    if (ext.c_mode <= 2)
-      SOPRO_CHECK_ARG(d && (reinterpret_cast<uintptr_t>(d) & 127u) == 0 && (ldd & 31) == 0 && (dseg & 31) == 0 && ldd >= g.N,
-                      "split-form output rows must start on 128-byte boundaries (ld, seg stride multiples of 32)");
-    else
-      SOPRO_CHECK_ARG(d && aligned16(d) && (ldd & 3) == 0 && (dseg & 3) == 0 && ldd >= g.N,
-                      "activated output rows must be 16-byte aligned (ld, seg stride multiples of 4)");
-  }
+  if (int rc = gemm_check_out_rows(__func__, g, ext, true)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (ext.c_mode) {
     case 0: return launch_8p<SOPRO_EPI_NONE, 0>(g, w_rows, ext, s);

@@ -15,6 +15,7 @@
 // coalesced dwordx4 loads (1 KB per instruction, every byte used once), so W never touches LDS.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -658,9 +659,90 @@ int launch_cfg6(const sopro_gemm_args& g, const uint4* wp, int ksubs, const sopr
   return -2;
 }
 
+// ---- Host side: the tile a call launches, the K slices it is offered, the argument checks and the four entry points
+// The tile shapes in use: WM x WN waves per workgroup, TM x TN MFMA tiles of 32 x 32 per wave.  T128_W8: see eight_waves; T128_W1x4 (developer
+// build): four waves of 128 x 32, no W fragment is requested twice
+#define SOPRO_TILES(X) \
+  X(T64, 2, 2, 1, 1) X(T64x128, 2, 2, 1, 2) X(T128x64, 2, 2, 2, 1) X(T128, 2, 2, 2, 2) X(T256x128, 2, 2, 4, 2) X(T128_W8, 2, 4, 2, 1) X(T128_W1x4, 1, 4, 4, 1)
+#define SOPRO_TILE(T, WM, WN, TM, TN) T,
+enum Tile { SOPRO_TILES(SOPRO_TILE) };
+#undef SOPRO_TILE
+struct TileSize { int bm, bn; };
+TileSize tile_size(Tile t) {
+#define SOPRO_TILE(T, WM, WN, TM, TN) if (t == T) return {WM * TM * 32, WN * TN * 32};
+  SOPRO_TILES(SOPRO_TILE)
+#undef SOPRO_TILE
+  return {0, 0};
+}
+
+enum Family { BF16X1, BF16X3, BF16X6, F16X3 };
+
+// The tile a family launches by default (the entry points put the developer overrides and the arg-max rule on top).  Results do not
+// depend on the tile shape: every output element runs the same K loop.
+Tile default_tile(Family f, int M, int N, int epilogue) {
+  const Tile small = epilogue == SOPRO_EPI_GLU ? T64x128 : T64;  // GLU: a value / gate tile pair per wave
+  switch (f) {
+    case BF16X3:
+      // few columns, or few rows (streaming chunks, batch 1: small tiles keep the split-K partial sums small): 64x64
+      return (N <= 64 || M <= 64) ? T64 : T128;
+    case BF16X1: {
+      // few output tiles (NAR's few-thousand-row shapes, streaming chunks): small tiles; the decoder's big shapes: 128x128
+      const int64_t t128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
+      return (N <= 64 || M <= 64 || t128 < 256) ? small : T128;
+    }
+    case BF16X6:
+      // measured on the NAR shapes (tools/gemm_x6_probe.py): a few thousand rows, K <= 1536 -> the small tiles win
+      return small;
+    case F16X3:
+      // many rows (64-utterance passes of the pipeline: 12800 rows): 128x128 tiles - NAR phase 5.8 -> 5.5-5.7 ms per step in the
+      // pipeline (profiles/r03_experiments.md); a few thousand rows and below: the small tiles (tools/gemm_x6_probe.py)
+      return M >= 8192 ? T128 : small;
+  }
+  return T64;
+}
+
+enum Form { FORM_CFG3, FORM_CFG6, FORM_ARGMAX };
+
+// The tiles a (family, form) is built for: this decides the set of gemm_bf16s_kernel instantiations
+template <int NPL, bool F16, Form FORM>
+constexpr bool has_tile(Tile t) {
+#ifdef SOPRO_DEV_SWITCHES
+  if (t == T128_W1x4) return NPL == 2 && FORM == (F16 ? FORM_CFG6 : FORM_CFG3);
+#endif
+  if (t == T64 || t == T128) return true;
+  if (FORM != FORM_CFG3) return t == (FORM == FORM_ARGMAX ? T128x64 : T64x128);
+  return NPL == 2 && (t == T128x64 || t == T256x128 || t == T128_W8);
+}
+
+struct Call {  // an entry point's own copy of its arguments (see prepare)
+  sopro_gemm_args g;
+  sopro_gemm_split_ext ext;
+  const uint4* wp;
+  int ksubs;
+  hipStream_t s;
+};
+
+template <int NPL, bool F16, Form FORM>
+int launch_tile(Tile t, const Call& c) {
+  switch (t) {
+#define SOPRO_TILE(T, WM, WN, TM, TN)                                                                                                     \
+  case T:                                                                                                                                 \
+    if constexpr (!has_tile<NPL, F16, FORM>(T)) break;                                                                                    \
+    else if constexpr (FORM == FORM_ARGMAX) return launch_one<NPL, WM, WN, TM, TN, SOPRO_EPI_NONE, 0, 5, F16>(c.g, c.wp, c.ksubs, c.ext, c.s); \
+    else if constexpr (FORM == FORM_CFG6) return launch_cfg6<NPL, WM, WN, TM, TN, F16>(c.g, c.wp, c.ksubs, c.ext, c.s);                  \
+    else return launch_cfg3<NPL, WM, WN, TM, TN>(c.g, c.wp, c.ksubs, c.ext, c.s);
+    SOPRO_TILES(SOPRO_TILE)
+#undef SOPRO_TILE
+  }
+  sopro_set_error("tile %d is not built for this kernel family", (int)t);
+  return -2;
+}
+
 // c_mode 5: per-row arg-max partials instead of C (64x64 tiles: 32 partials per 2048 columns)
 template <int NPL, bool F16 = false>
-int launch_argmax(sopro_gemm_args& g, const uint4* wp, int ksubs, const sopro_gemm_split_ext& ext, hipStream_t s) {
+int launch_argmax(const Call& c) {
+  const sopro_gemm_args& g = c.g;
+  const sopro_gemm_split_ext& ext = c.ext;
   SOPRO_CHECK_ARG(g.epilogue == SOPRO_EPI_NONE && g.prologue == SOPRO_PRO_NONE && !ext.rms_norm && ext.a_format == 0,
                   "arg-max output takes a plain contraction (no prologue / epilogue / fused norm)");
   SOPRO_CHECK_ARG(ext.C2 && ext.ldc2 >= (g.N + 63) / 64, "arg-max output: C2 = [M][ldc2 >= ceil(N / 64)] (value, index) pairs");
@@ -671,9 +753,9 @@ int launch_argmax(sopro_gemm_args& g, const uint4* wp, int ksubs, const sopro_ge
   // staged A row serves 128 columns instead of 64 - half the A traffic and half the split work per product; pairs stay per 64 columns.
   // SOPRO_ARGMAX_TN=1 (developer A/B): the round-5 128 x 64 tiles
   static const bool tn1 = SOPRO_DEV_ENV("SOPRO_ARGMAX_TN") != nullptr && SOPRO_DEV_ENV("SOPRO_ARGMAX_TN")[0] == '1';
-  if (g.M >= 8192 && g.N >= 2048 && (g.N & 127) == 0 && !tm1 && !tn1) return launch_one<NPL, 2, 2, 2, 2, SOPRO_EPI_NONE, 0, 5, F16>(g, wp, ksubs, ext, s);
-  if (g.M >= 8192 && !tm1) return launch_one<NPL, 2, 2, 2, 1, SOPRO_EPI_NONE, 0, 5, F16>(g, wp, ksubs, ext, s);
-  return launch_one<NPL, 2, 2, 1, 1, SOPRO_EPI_NONE, 0, 5, F16>(g, wp, ksubs, ext, s);
+  Tile t = T64;
+  if (g.M >= 8192 && !tm1) t = (g.N >= 2048 && (g.N & 127) == 0 && !tn1) ? T128 : T128x64;
+  return launch_tile<NPL, F16, FORM_ARGMAX>(t, c);
 }
 
 int check_rope(const sopro_gemm_args& g, const sopro_gemm_split_ext& ext) {
@@ -705,27 +787,66 @@ int check_ln(const sopro_gemm_args& g, const sopro_gemm_split_ext& ext) {
 }
 
 int check_common(sopro_gemm_args& g, sopro_gemm_split_ext& ext, const void* packed_w) {
-  if (g.a_seg_stride == 0) g.a_seg_stride = (int64_t)g.rows_per_seg * g.lda;
-  if (g.c_seg_stride == 0) g.c_seg_stride = (int64_t)g.rows_per_seg * g.ldc;
-  if (g.r_seg_stride == 0) g.r_seg_stride = (int64_t)g.rows_per_seg * g.ldr;
-  if (ext.c2_seg_stride == 0) ext.c2_seg_stride = (int64_t)g.rows_per_seg * ext.ldc2;
-  SOPRO_CHECK_ARG(g.M > 0 && g.N > 0 && g.K > 0, "M, N, K must be positive");
-  SOPRO_CHECK_ARG((g.K & 3) == 0, "K must be a multiple of 4");
-  SOPRO_CHECK_ARG(g.rows_per_seg > 0, "rows_per_seg must be positive");
-  SOPRO_CHECK_ARG(g.A && packed_w && (g.C || ext.c_mode == 5), "A, packed_w, C must be non-NULL");
-  SOPRO_CHECK_ARG(aligned16(g.A) && aligned16(packed_w), "A and packed_w must be 16-byte aligned");
-  SOPRO_CHECK_ARG((g.lda & 3) == 0 && (g.a_seg_stride & 3) == 0, "lda, a_seg_stride must be multiples of 4");
-  SOPRO_CHECK_ARG(g.epilogue != SOPRO_EPI_RES || g.R != nullptr, "EPI_RES needs R");
-  SOPRO_CHECK_ARG(g.prologue != SOPRO_PRO_ADDVEC || (g.pro_vec && aligned16(g.pro_vec)), "PRO_ADDVEC needs an aligned pro_vec");
-  SOPRO_CHECK_ARG(g.epilogue != SOPRO_EPI_GLU || (g.N % 64) == 0, "EPI_GLU needs N % 64 == 0 (packed value/gate blocks)");
+  if (int rc = gemm_check_basic(__func__, g, &ext, packed_w, GEMM_PACKED_W)) return rc;
   SOPRO_CHECK_ARG(ext.ksplit >= 0 && ext.ksplit <= 64, "ksplit must be in 0..64");
   SOPRO_CHECK_ARG(ext.ksplit <= 1 || g.dbg == nullptr, "the clock-stamp probe is for unsplit launches");
   return 0;
 }
 
+// Fused RMSNorm of the A rows (sopro_gemm_split_ext.rms_norm).  `plain_out`: the one-pass entry, which has other output modes, also
+// wants c_mode 0 under it.
+int check_rms(const char* who, const sopro_gemm_args& g, const sopro_gemm_split_ext& ext, bool plain_out) {
+  SOPRO_CHECK_AS(who, !ext.rms_norm || ((g.K & 31) == 0 && ext.ksplit <= 1 && g.prologue == SOPRO_PRO_NONE && ext.rms_eps > 0.f && (!plain_out || ext.c_mode == 0)),
+                 plain_out ? "fused RMSNorm needs K % 32 == 0, no split-K, no prologue, eps > 0 and a plain output"
+                           : "fused RMSNorm needs K % 32 == 0, no split-K, no prologue and eps > 0");
+  return 0;
+}
+
+int g_group_m = 0;
+
+// What every entry point does first: its own copy of the arguments (a NULL ext = all zero, unless the family needs one), the default tile
+// walk, the family's operand-form rules `forms` where they come before the common ones, the common and the LayerNorm checks.
+typedef int (*forms_check)(const char* who, const sopro_gemm_args& g, const sopro_gemm_split_ext& ext);
+int prepare(const char* who, const sopro_gemm_args* a, const void* packed_w, const sopro_gemm_split_ext* x, void* stream, bool ext_required,
+            forms_check forms, Call& c) {
+  SOPRO_CHECK_AS(who, a != nullptr && (x != nullptr || !ext_required), ext_required ? "args / ext is NULL (ext carries acc_scale)" : "args is NULL");
+  c.g = *a;
+  memset(&c.ext, 0, sizeof(c.ext));
+  if (x) c.ext = *x;
+  if (c.ext.group_m == 0) c.ext.group_m = g_group_m;
+  if (forms)
+    if (int rc = forms(who, c.g, c.ext)) return rc;
+  if (int rc = check_common(c.g, c.ext, packed_w)) return rc;
+  if (int rc = check_ln(c.g, c.ext)) return rc;
+  c.wp = reinterpret_cast<const uint4*>(packed_w);
+  c.ksubs = (c.g.K + 31) / 32 * 2;
+  c.s = reinterpret_cast<hipStream_t>(stream);
+  return 0;
+}
+
+int forms_bf16x1(const char* who, const sopro_gemm_args& g, const sopro_gemm_split_ext& ext) {
+  SOPRO_CHECK_AS(who, (ext.a_format == 0 || ext.a_format == 2) && (ext.c_mode == 0 || (ext.c_mode >= 3 && ext.c_mode <= 8)),
+                 "bf16x1 reads fp32 rows (a_format 0) or bf16 rows (2) and writes fp32 rows (c_mode 0, 3, 4), arg-max partials (5) or bf16 rows (6, 7, 8)");
+  if (ext.a_format == 2 || ext.c_mode >= 6) {
+    SOPRO_CHECK_AS(who, !ext.rms_norm && g.prologue == SOPRO_PRO_NONE && (g.epilogue == SOPRO_EPI_NONE || g.epilogue == SOPRO_EPI_RES),
+                   "bf16 rows: no prologue / fused norm, epilogue NONE or RES (the activation is applied by the producer: c_mode 7 / 8)");
+    SOPRO_CHECK_AS(who, ext.a_format != 2 || ((g.lda & 3) == 0 && (g.a_seg_stride & 3) == 0), "bf16 A rows: lda, a_seg_stride multiples of 4 elements");
+    SOPRO_CHECK_AS(who, g.epilogue != SOPRO_EPI_RES || ext.c_mode >= 6, "EPI_RES with bf16 A writes bf16 rows (its skip operand R is bf16 then)");
+  }
+  return check_rms(who, g, ext, true);
+}
+
+template <bool F16>  // the six-pass and the f16 three-pass entry
+int forms_x6(const char* who, const sopro_gemm_args& g, const sopro_gemm_split_ext& ext) {
+  if (F16) SOPRO_CHECK_AS(who, ext.acc_scale > 0.f, "acc_scale = 1 / (sopro_f16x3_a_scale() * the weight's pack scale) must be set");
+  SOPRO_CHECK_AS(who, ext.a_format == 0 && (ext.c_mode == 0 || ext.c_mode == 5),
+                 F16 ? "the f16 three-pass path reads fp32 rows and writes fp32 rows, or arg-max partials (c_mode 5)"
+                     : "the six-pass path reads fp32 rows and writes fp32 rows, or arg-max partials (c_mode 5)");
+  return check_rms(who, g, ext, false);
+}
+
 }  // namespace
 
-static int g_group_m = 0;
 extern "C" int sopro_gemm_set_group_m(int g) {
   g_group_m = g > 1 ? g : 0;
   return 0;
@@ -754,6 +875,29 @@ extern "C" int sopro_gemm_bf16_set_tile_override(int cfg) {
   return 0;
 }
 
+// K slices for a problem of M x N x K on the default tile of its kernel family (pieces 1: one-pass, 2: three-pass, 3: six-pass; f16:
+// the f16 three-pass family), for a caller with `ws_bytes` of workspace and `n_tickets` tickets; 1 = no split.  The split costs ~10 us
+// (device-scope release / acquire around the ticket): it pays from ~32 K-steps up; a slice costs ~0.9 us per K-step, the reducing
+// workgroup ~0.36 us per slice: ks ~ sqrt(2.5 * K-steps).  SOPRO_NO_SPLITK=1 (developer switch): always 1.
+// The long-K form needs no case of its own: sopro_gemm_8p_takes wants >= 128 tiles of 256 x 256 with N % 256 == 0, which is >= 96
+// tiles of the shape modelled here for any M, so the answer for a call it takes is 1.
+extern "C" int sopro_gemm_auto_ksplit(int32_t M, int32_t N, int32_t K, int32_t pieces, int32_t f16, int32_t epilogue, int64_t ws_bytes, int32_t n_tickets) {
+  static const bool no_splitk = getenv("SOPRO_NO_SPLITK") && getenv("SOPRO_NO_SPLITK")[0] == '1';
+  if (no_splitk || M <= 0 || N <= 0 || K <= 0) return 1;
+  // f16 launches 128 x 128 tiles from M = 8192 (fewer than 96 of them up to M = 12160 at N <= 128): the rule was measured on the small tiles, >= 128 there, and keeps their answer
+  if (f16 && M >= 8192) return 1;
+  const TileSize t = tile_size(default_tile(f16 ? F16X3 : pieces == 3 ? BF16X6 : pieces == 1 ? BF16X1 : BF16X3, M, N, epilogue));
+  const int64_t tiles = (int64_t)((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
+  const int kt = (K + 31) / 32;
+  if (tiles >= 96 || kt < 32 || tiles > n_tickets) return 1;
+  int ks = (int)lrint(sqrt(2.5 * kt));
+  if (ks > 16) ks = 16;
+  if (ks > 512 / (int)tiles) ks = 512 / (int)tiles;
+  if (ks < 1) ks = 1;
+  while (ks > 1 && (int64_t)ks * tiles * t.bm * t.bn * 4 > ws_bytes) --ks;
+  return ks;
+}
+
 extern "C" int64_t sopro_packed_w_bytes(int32_t N, int32_t K, int32_t pieces) {
   if (N <= 0 || K <= 0 || pieces < 1 || pieces > 3) return 0;
   return (int64_t)((N + 31) / 32) * ((K + 31) / 32 * 2) * pieces * 64 * 16;
@@ -776,14 +920,10 @@ extern "C" int sopro_pack_w_bf16(const float* W, int64_t ldw, int32_t N, int32_t
 }
 
 extern "C" int sopro_gemm_bf16x3(const sopro_gemm_args* a, const void* packed_w, const sopro_gemm_split_ext* x, void* stream) {
-  SOPRO_CHECK_ARG(a != nullptr, "args is NULL");
-  sopro_gemm_args g = *a;
-  sopro_gemm_split_ext ext;
-  memset(&ext, 0, sizeof(ext));
-  if (x) ext = *x;
-  if (ext.group_m == 0) ext.group_m = g_group_m;
-  if (int rc = check_common(g, ext, packed_w)) return rc;
-  if (int rc = check_ln(g, ext)) return rc;
+  Call c;
+  if (int rc = prepare(__func__, a, packed_w, x, stream, false, nullptr, c)) return rc;
+  const sopro_gemm_args& g = c.g;
+  const sopro_gemm_split_ext& ext = c.ext;
   SOPRO_CHECK_ARG(g.prologue == SOPRO_PRO_NONE || g.prologue == SOPRO_PRO_ELU, "prologue must be NONE or ELU");
   SOPRO_CHECK_ARG(g.epilogue == SOPRO_EPI_NONE || g.epilogue == SOPRO_EPI_GELU || g.epilogue == SOPRO_EPI_RES || g.epilogue == SOPRO_EPI_ROPE,
                   "epilogue must be NONE, GELU, RES or ROPE");
@@ -796,131 +936,78 @@ extern "C" int sopro_gemm_bf16x3(const sopro_gemm_args* a, const void* packed_w,
                     "split-form A: K, lda, a_seg_stride multiples of 32 and a 128-byte aligned base");
   }
   SOPRO_CHECK_ARG(ext.c_mode >= 0 && ext.c_mode <= 4, "c_mode must be 0..4");
-  if (ext.c_mode != 0) {
-    SOPRO_CHECK_ARG((g.N & 3) == 0, "activated output: N % 4 == 0");
-    const bool second = ext.c_mode == 2 || ext.c_mode == 4;
-    float* d = second ? ext.C2 : g.C;
-    const int64_t ldd = second ? ext.ldc2 : g.ldc, dseg = second ? ext.c2_seg_stride : g.c_seg_stride;
-    if (ext.c_mode <= 2)
-      SOPRO_CHECK_ARG(d && (reinterpret_cast<uintptr_t>(d) & 127u) == 0 && (ldd & 31) == 0 && (dseg & 31) == 0 && ldd >= g.N,
-                      "split-form output rows must start on 128-byte boundaries (ld, seg stride multiples of 32)");
-    else
-      SOPRO_CHECK_ARG(d && aligned16(d) && (ldd & 3) == 0 && (dseg & 3) == 0 && ldd >= g.N,
-                      "activated output rows must be 16-byte aligned (ld, seg stride multiples of 4)");
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint4* wp = reinterpret_cast<const uint4*>(packed_w);
-  const int ksubs = (g.K + 31) / 32 * 2;
+  if (int rc = gemm_check_out_rows(__func__, g, ext, true)) return rc;
   // The activation-stationary form for short K (gemm_astat.hip; bit-identical results) is a developer override (9): measured at
   // 0.85-1.0x of the tile kernel on every K <= 512 shape of the decoder / refinement (profiles/r05_experiments.md section 4)
 #ifdef SOPRO_DEV_SWITCHES
-  if (g_tile_override == 9 && sopro_gemm_astat_takes(g, ext)) return sopro_gemm_astat_bf16x3(g, packed_w, s);
+  if (g_tile_override == 9 && sopro_gemm_astat_takes(g, ext)) return sopro_gemm_astat_bf16x3(g, packed_w, c.s);
 #endif
-  switch (g_tile_override) {
-    case 1: return launch_cfg3<2, 2, 2, 2, 2>(g, wp, ksubs, ext, s);
-    case 2: return launch_cfg3<2, 2, 2, 4, 2>(g, wp, ksubs, ext, s);
-    case 4: return launch_cfg3<2, 2, 2, 2, 1>(g, wp, ksubs, ext, s);
-    case 5: return launch_cfg3<2, 2, 2, 1, 1>(g, wp, ksubs, ext, s);
-    case 7: return launch_cfg3<2, 2, 4, 2, 1>(g, wp, ksubs, ext, s);  // 128x128 on eight waves
-#ifdef SOPRO_DEV_SWITCHES
-    case 3: return launch_cfg3<2, 1, 4, 4, 1>(g, wp, ksubs, ext, s);  // 128x128, four waves of 128 x 32: no W fragment is requested twice
-#endif
-    default: break;
-  }
-  // few columns, or few rows (streaming chunks, batch 1: small tiles keep the split-K partial sums small): 64x64
-  if (g.N <= 64 || g.M <= 64) return launch_cfg3<2, 2, 2, 1, 1>(g, wp, ksubs, ext, s);
-  if (eight_waves(g)) return launch_cfg3<2, 2, 4, 2, 1>(g, wp, ksubs, ext, s);
+  Tile t = default_tile(BF16X3, g.M, g.N, g.epilogue);
   // developer A/B (SOPRO_GEMM_NARROW=1): 128x64 tiles for the N <= 512 contractions of a many-row pass (o / fc2 of the decoder transformer at
   // 25600 rows: 800 tiles of 128x128 on 384 slots of the 192-CU partition = a third round that is 8 % full).  Measured in the pipeline
   // (r05 call 22): decode 13.21 / 13.25 -> 13.38 / 13.37 ms per step - the narrower tile loses more than the fuller last round wins: no-go
   static const bool narrow = SOPRO_DEV_ENV("SOPRO_GEMM_NARROW") != nullptr && SOPRO_DEV_ENV("SOPRO_GEMM_NARROW")[0] == '1';
-  if (narrow && g.N <= 512 && g.M >= 8192) return launch_cfg3<2, 2, 2, 2, 1>(g, wp, ksubs, ext, s);
-  return launch_cfg3<2, 2, 2, 2, 2>(g, wp, ksubs, ext, s);
+  if (t == T128 && eight_waves(g)) t = T128_W8;
+  else if (t == T128 && narrow && g.N <= 512 && g.M >= 8192) t = T128x64;
+  switch (g_tile_override) {
+    case 1: t = T128; break;
+    case 2: t = T256x128; break;
+    case 4: t = T128x64; break;
+    case 5: t = T64; break;
+    case 7: t = T128_W8; break;
+#ifdef SOPRO_DEV_SWITCHES
+    case 3: t = T128_W1x4; break;
+#endif
+    default: break;
+  }
+  return launch_tile<2, false, FORM_CFG3>(t, c);
 }
 
 // bf16 mode: one pass.  Takes what either split entry point takes, except split-form operands (a_format 1, c_mode 1 / 2).
 extern "C" int sopro_gemm_bf16x1(const sopro_gemm_args* a, const void* packed_w, const sopro_gemm_split_ext* x, void* stream) {
-  SOPRO_CHECK_ARG(a != nullptr, "args is NULL");
-  sopro_gemm_args g = *a;
-  sopro_gemm_split_ext ext;
-  memset(&ext, 0, sizeof(ext));
-  if (x) ext = *x;
-  if (ext.group_m == 0) ext.group_m = g_group_m;
-  SOPRO_CHECK_ARG((ext.a_format == 0 || ext.a_format == 2) && (ext.c_mode == 0 || (ext.c_mode >= 3 && ext.c_mode <= 8)),
-                  "bf16x1 reads fp32 rows (a_format 0) or bf16 rows (2) and writes fp32 rows (c_mode 0, 3, 4), arg-max partials (5) or bf16 rows (6, 7, 8)");
-  if (ext.a_format == 2 || ext.c_mode >= 6) {
-    SOPRO_CHECK_ARG(!ext.rms_norm && g.prologue == SOPRO_PRO_NONE && (g.epilogue == SOPRO_EPI_NONE || g.epilogue == SOPRO_EPI_RES),
-                    "bf16 rows: no prologue / fused norm, epilogue NONE or RES (the activation is applied by the producer: c_mode 7 / 8)");
-    SOPRO_CHECK_ARG(ext.a_format != 2 || ((g.lda & 3) == 0 && (g.a_seg_stride & 3) == 0), "bf16 A rows: lda, a_seg_stride multiples of 4 elements");
-    SOPRO_CHECK_ARG(g.epilogue != SOPRO_EPI_RES || ext.c_mode >= 6, "EPI_RES with bf16 A writes bf16 rows (its skip operand R is bf16 then)");
-  }
-  SOPRO_CHECK_ARG(!ext.rms_norm || ((g.K & 31) == 0 && ext.ksplit <= 1 && g.prologue == SOPRO_PRO_NONE && ext.rms_eps > 0.f && ext.c_mode == 0),
-                  "fused RMSNorm needs K % 32 == 0, no split-K, no prologue, eps > 0 and a plain output");
-  if (int rc = check_common(g, ext, packed_w)) return rc;
-  if (int rc = check_ln(g, ext)) return rc;
-  if (ext.c_mode == 5) return launch_argmax<1>(g, reinterpret_cast<const uint4*>(packed_w), (g.K + 31) / 32 * 2, ext, reinterpret_cast<hipStream_t>(stream));
-  if (ext.c_mode >= 6) {  // bf16 rows: C (and C2 for c_mode 8; R for EPI_RES) point at bf16 elements, strides count elements
-    SOPRO_CHECK_ARG((g.N & 3) == 0 && g.C && (reinterpret_cast<uintptr_t>(g.C) & 7u) == 0 && (g.ldc & 3) == 0 && (g.c_seg_stride & 3) == 0 && g.ldc >= g.N,
-                    "bf16 output rows must be 8-byte aligned (N, ld, seg stride multiples of 4)");
-    SOPRO_CHECK_ARG(ext.c_mode != 8 || (ext.C2 && (reinterpret_cast<uintptr_t>(ext.C2) & 7u) == 0 && (ext.ldc2 & 3) == 0 && (ext.c2_seg_stride & 3) == 0 && ext.ldc2 >= g.N),
-                    "c_mode 8: C2 (the activated bf16 copy) must be given, 8-byte aligned rows");
-    SOPRO_CHECK_ARG(g.epilogue != SOPRO_EPI_RES || ((reinterpret_cast<uintptr_t>(g.R) & 7u) == 0 && (g.ldr & 3) == 0 && (g.r_seg_stride & 3) == 0),
-                    "bf16 skip operand rows must be 8-byte aligned");
-  } else if (ext.c_mode != 0) {
-    const bool second = ext.c_mode == 4;
-    float* d = second ? ext.C2 : g.C;
-    const int64_t ldd = second ? ext.ldc2 : g.ldc, dseg = second ? ext.c2_seg_stride : g.c_seg_stride;
-    SOPRO_CHECK_ARG((g.N & 3) == 0 && d && aligned16(d) && (ldd & 3) == 0 && (dseg & 3) == 0 && ldd >= g.N,
-                    "activated output rows must be 16-byte aligned (N, ld, seg stride multiples of 4)");
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint4* wp = reinterpret_cast<const uint4*>(packed_w);
-  const int ksubs = (g.K + 31) / 32 * 2;
-  // few output tiles (NAR's few-thousand-row shapes, streaming chunks): small tiles; the decoder's big shapes: 128x128
-  const int64_t t128 = (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128);
-  const bool small = g.N <= 64 || g.M <= 64 || t128 < 256;
-  const bool nar_like = ext.rms_norm || g.epilogue == SOPRO_EPI_GLU || g.prologue == SOPRO_PRO_ADDVEC;
-  if (nar_like) {
+  Call c;
+  if (int rc = prepare(__func__, a, packed_w, x, stream, false, forms_bf16x1, c)) return rc;
+  const sopro_gemm_args& g = c.g;
+  const sopro_gemm_split_ext& ext = c.ext;
+  if (ext.c_mode == 5) return launch_argmax<1>(c);
+  if (int rc = gemm_check_out_rows(__func__, g, ext, false)) return rc;
+  const Tile t = default_tile(BF16X1, g.M, g.N, g.epilogue);
+  if (ext.rms_norm || g.epilogue == SOPRO_EPI_GLU || g.prologue == SOPRO_PRO_ADDVEC) {  // the forms of the six-pass entry (NAR)
     SOPRO_CHECK_ARG(ext.c_mode == 0 && (g.prologue == SOPRO_PRO_NONE || g.prologue == SOPRO_PRO_ADDVEC), "GLU / RMSNorm / ADDVEC forms write plain fp32");
-    if (g.epilogue == SOPRO_EPI_GLU) return small ? launch_cfg6<1, 2, 2, 1, 2>(g, wp, ksubs, ext, s) : launch_cfg6<1, 2, 2, 2, 2>(g, wp, ksubs, ext, s);
-    return small ? launch_cfg6<1, 2, 2, 1, 1>(g, wp, ksubs, ext, s) : launch_cfg6<1, 2, 2, 2, 2>(g, wp, ksubs, ext, s);
+    return launch_tile<1, false, FORM_CFG6>(t, c);
   }
-  SOPRO_CHECK_ARG(g.prologue == SOPRO_PRO_NONE || g.prologue == SOPRO_PRO_ELU, "prologue must be NONE, ELU or ADDVEC");
+  SOPRO_CHECK_ARG(g.prologue == SOPRO_PRO_NONE || g.prologue == SOPRO_PRO_ELU, "prologue must be NONE or ELU (or ADDVEC, with a plain fp32 output)");
   SOPRO_CHECK_ARG(g.epilogue == SOPRO_EPI_NONE || g.epilogue == SOPRO_EPI_GELU || g.epilogue == SOPRO_EPI_RES || g.epilogue == SOPRO_EPI_ROPE,
-                  "epilogue must be NONE, GELU, RES, GLU or ROPE");
+                  "epilogue must be NONE, GELU, RES or ROPE (or GLU, with a plain fp32 output)");
   if (int rc = check_rope(g, ext)) return rc;
-  return small ? launch_cfg3<1, 2, 2, 1, 1>(g, wp, ksubs, ext, s) : launch_cfg3<1, 2, 2, 2, 2>(g, wp, ksubs, ext, s);
+  return launch_tile<1, false, FORM_CFG3>(t, c);
+}
+
+// The six-pass entry and the f16 three-pass one take the same forms.  `env_tile`: SOPRO_F16X3_TILE (the many-row rule is off under it)
+template <int NPL, bool F16>
+static int gemm_x6(const char* who, const sopro_gemm_args* a, const void* packed_w, const sopro_gemm_split_ext* x, void* stream, int env_tile) {
+  Call c;
+  if (int rc = prepare(who, a, packed_w, x, stream, F16, forms_x6<F16>, c)) return rc;
+  SOPRO_CHECK_AS(who, c.g.prologue == SOPRO_PRO_NONE || c.g.prologue == SOPRO_PRO_ADDVEC, "prologue must be NONE or ADDVEC");
+  SOPRO_CHECK_AS(who, c.g.epilogue == SOPRO_EPI_NONE || c.g.epilogue == SOPRO_EPI_GELU || c.g.epilogue == SOPRO_EPI_RES || c.g.epilogue == SOPRO_EPI_GLU,
+                 "epilogue must be NONE, GELU, RES or GLU");
+  if (c.ext.c_mode == 5) return launch_argmax<NPL, F16>(c);
+  const Tile small = default_tile(BF16X6, c.g.M, c.g.N, c.g.epilogue);
+  Tile t = env_tile ? small : default_tile(F16 ? F16X3 : BF16X6, c.g.M, c.g.N, c.g.epilogue);
+  switch (g_tile_override ? g_tile_override : env_tile) {
+    case 1: t = T128; break;
+#ifdef SOPRO_DEV_SWITCHES
+    case 3: if (F16) t = T128_W1x4; break;
+#endif
+    case 4: t = T64x128; break;
+    case 5: t = small; break;
+    default: break;
+  }
+  return launch_tile<NPL, F16, FORM_CFG6>(t, c);
 }
 
 extern "C" int sopro_gemm_bf16x6(const sopro_gemm_args* a, const void* packed_w, const sopro_gemm_split_ext* x, void* stream) {
-  SOPRO_CHECK_ARG(a != nullptr, "args is NULL");
-  sopro_gemm_args g = *a;
-  sopro_gemm_split_ext ext;
-  memset(&ext, 0, sizeof(ext));
-  if (x) ext = *x;
-  if (ext.group_m == 0) ext.group_m = g_group_m;
-  SOPRO_CHECK_ARG(ext.a_format == 0 && (ext.c_mode == 0 || ext.c_mode == 5),
-                  "the six-pass path reads fp32 rows and writes fp32 rows, or arg-max partials (c_mode 5)");
-  SOPRO_CHECK_ARG(!ext.rms_norm || ((g.K & 31) == 0 && ext.ksplit <= 1 && g.prologue == SOPRO_PRO_NONE && ext.rms_eps > 0.f),
-                  "fused RMSNorm needs K % 32 == 0, no split-K, no prologue and eps > 0");
-  if (int rc = check_common(g, ext, packed_w)) return rc;
-  if (int rc = check_ln(g, ext)) return rc;
-  SOPRO_CHECK_ARG(g.prologue == SOPRO_PRO_NONE || g.prologue == SOPRO_PRO_ADDVEC, "prologue must be NONE or ADDVEC");
-  SOPRO_CHECK_ARG(g.epilogue == SOPRO_EPI_NONE || g.epilogue == SOPRO_EPI_GELU || g.epilogue == SOPRO_EPI_RES || g.epilogue == SOPRO_EPI_GLU,
-                  "epilogue must be NONE, GELU, RES or GLU");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint4* wp = reinterpret_cast<const uint4*>(packed_w);
-  const int ksubs = (g.K + 31) / 32 * 2;
-  if (ext.c_mode == 5) return launch_argmax<3>(g, wp, ksubs, ext, s);
-  switch (g_tile_override) {
-    case 1: return launch_cfg6<3, 2, 2, 2, 2>(g, wp, ksubs, ext, s);
-    case 4: return launch_cfg6<3, 2, 2, 1, 2>(g, wp, ksubs, ext, s);
-    case 5: if (g.epilogue != SOPRO_EPI_GLU) return launch_cfg6<3, 2, 2, 1, 1>(g, wp, ksubs, ext, s); break;
-    default: break;
-  }
-  // measured on the NAR shapes (tools/gemm_x6_probe.py): a few thousand rows, K <= 1536 -> the small tiles win
-  if (g.epilogue == SOPRO_EPI_GLU) return launch_cfg6<3, 2, 2, 1, 2>(g, wp, ksubs, ext, s);
-  return launch_cfg6<3, 2, 2, 1, 1>(g, wp, ksubs, ext, s);
+  return gemm_x6<3, false>(__func__, a, packed_w, x, stream, 0);
 }
 
 // ---- f16x3: the token paths at three passes (see A16_SCALE above)
@@ -939,38 +1026,6 @@ extern "C" int sopro_pack_w_f16x2(const float* W, int64_t ldw, int32_t N, int32_
 extern "C" float sopro_f16x3_a_scale(void) { return A16_SCALE; }
 
 extern "C" int sopro_gemm_f16x3(const sopro_gemm_args* a, const void* packed_w, const sopro_gemm_split_ext* x, void* stream) {
-  SOPRO_CHECK_ARG(a != nullptr && x != nullptr, "args / ext is NULL (ext carries acc_scale)");
-  sopro_gemm_args g = *a;
-  sopro_gemm_split_ext ext = *x;
-  if (ext.group_m == 0) ext.group_m = g_group_m;
-  SOPRO_CHECK_ARG(ext.acc_scale > 0.f, "acc_scale = 1 / (sopro_f16x3_a_scale() * the weight's pack scale) must be set");
-  SOPRO_CHECK_ARG(ext.a_format == 0 && (ext.c_mode == 0 || ext.c_mode == 5),
-                  "the f16 three-pass path reads fp32 rows and writes fp32 rows, or arg-max partials (c_mode 5)");
-  SOPRO_CHECK_ARG(!ext.rms_norm || ((g.K & 31) == 0 && ext.ksplit <= 1 && g.prologue == SOPRO_PRO_NONE && ext.rms_eps > 0.f),
-                  "fused RMSNorm needs K % 32 == 0, no split-K, no prologue and eps > 0");
-  if (int rc = check_common(g, ext, packed_w)) return rc;
-  if (int rc = check_ln(g, ext)) return rc;
-  SOPRO_CHECK_ARG(g.prologue == SOPRO_PRO_NONE || g.prologue == SOPRO_PRO_ADDVEC, "prologue must be NONE or ADDVEC");
-  SOPRO_CHECK_ARG(g.epilogue == SOPRO_EPI_NONE || g.epilogue == SOPRO_EPI_GELU || g.epilogue == SOPRO_EPI_RES || g.epilogue == SOPRO_EPI_GLU,
-                  "epilogue must be NONE, GELU, RES or GLU");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint4* wp = reinterpret_cast<const uint4*>(packed_w);
-  const int ksubs = (g.K + 31) / 32 * 2;
-  if (ext.c_mode == 5) return launch_argmax<2, true>(g, wp, ksubs, ext, s);
   static const int env_tile = SOPRO_DEV_ENV("SOPRO_F16X3_TILE") ? atoi(SOPRO_DEV_ENV("SOPRO_F16X3_TILE")) : 0;  // developer A/B of this family alone
-  switch (g_tile_override ? g_tile_override : env_tile) {
-    case 1: return launch_cfg6<2, 2, 2, 2, 2, true>(g, wp, ksubs, ext, s);
-#ifdef SOPRO_DEV_SWITCHES
-    case 3: return launch_cfg6<2, 1, 4, 4, 1, true>(g, wp, ksubs, ext, s);
-#endif
-    case 4: return launch_cfg6<2, 2, 2, 1, 2, true>(g, wp, ksubs, ext, s);
-    case 5: return g.epilogue == SOPRO_EPI_GLU ? launch_cfg6<2, 2, 2, 1, 2, true>(g, wp, ksubs, ext, s) : launch_cfg6<2, 2, 2, 1, 1, true>(g, wp, ksubs, ext, s);
-    default: break;
-  }
-  // many rows (64-utterance passes of the pipeline: 12800 rows): 128x128 tiles - NAR phase 5.8 -> 5.5-5.7 ms per step in the
-  // pipeline (profiles/r03_experiments.md); a few thousand rows and below: the small tiles (tools/gemm_x6_probe.py).  Results
-  // do not depend on the tile shape (every output element runs the same K loop)
-  if (g.M >= 8192 && env_tile == 0) return launch_cfg6<2, 2, 2, 2, 2, true>(g, wp, ksubs, ext, s);
-  if (g.epilogue == SOPRO_EPI_GLU) return launch_cfg6<2, 2, 2, 1, 2, true>(g, wp, ksubs, ext, s);
-  return launch_cfg6<2, 2, 2, 1, 1, true>(g, wp, ksubs, ext, s);
+  return gemm_x6<2, true>(__func__, a, packed_w, x, stream, env_tile);
 }

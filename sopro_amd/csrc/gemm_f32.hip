@@ -8,6 +8,7 @@
 // B agree): lanes 0-31 carry k = 8c+s, lanes 32-63 carry k = 8c+4+s at MFMA step s.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -193,21 +194,9 @@ extern "C" int sopro_gemm_set_tile_override(int cfg) {
 extern "C" int sopro_gemm_f32(const sopro_gemm_args* a, void* stream) {
   SOPRO_CHECK_ARG(a != nullptr, "args is NULL");
   sopro_gemm_args g = *a;
-  // a zero segment stride means "dense": segments follow each other without padding rows
-  if (g.a_seg_stride == 0) g.a_seg_stride = (int64_t)g.rows_per_seg * g.lda;
-  if (g.c_seg_stride == 0) g.c_seg_stride = (int64_t)g.rows_per_seg * g.ldc;
-  if (g.r_seg_stride == 0) g.r_seg_stride = (int64_t)g.rows_per_seg * g.ldr;
-  SOPRO_CHECK_ARG(g.M > 0 && g.N > 0 && g.K > 0, "M, N, K must be positive");
-  SOPRO_CHECK_ARG((g.K & 3) == 0, "K must be a multiple of 4");
-  SOPRO_CHECK_ARG(g.rows_per_seg > 0, "rows_per_seg must be positive");
-  SOPRO_CHECK_ARG(g.A && g.W && g.C, "A, W, C must be non-NULL");
-  SOPRO_CHECK_ARG(aligned16(g.A) && aligned16(g.W), "A and W must be 16-byte aligned");
-  SOPRO_CHECK_ARG((g.lda & 3) == 0 && (g.ldw & 3) == 0 && (g.a_seg_stride & 3) == 0, "lda, ldw, a_seg_stride must be multiples of 4");
+  if (int rc = gemm_check_basic(__func__, g, nullptr, g.W, GEMM_F32_ROWS)) return rc;
   SOPRO_CHECK_ARG(g.prologue >= SOPRO_PRO_NONE && g.prologue <= SOPRO_PRO_ADDVEC, "unknown prologue");
   SOPRO_CHECK_ARG(g.epilogue >= SOPRO_EPI_NONE && g.epilogue <= SOPRO_EPI_TANH, "unknown epilogue");
-  SOPRO_CHECK_ARG(g.epilogue != SOPRO_EPI_RES || g.R != nullptr, "EPI_RES needs R");
-  SOPRO_CHECK_ARG(g.prologue != SOPRO_PRO_ADDVEC || (g.pro_vec && aligned16(g.pro_vec)), "PRO_ADDVEC needs an aligned pro_vec");
-  SOPRO_CHECK_ARG(g.epilogue != SOPRO_EPI_GLU || (g.N % 64) == 0, "EPI_GLU needs N % 64 == 0 (packed value/gate blocks)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (g_tile_override) {
     case 1: return launch_cfg<2, 2, 2, 2>(g, s);

@@ -236,30 +236,6 @@ struct SplitK {
   int32_t* tickets = nullptr;
 };
 
-// K slices for a problem of M x N x K on tiles of the kernel family `pieces` selects (3: six-pass / f16 three-pass rules,
-// 1: one-pass, 2: three-pass).  The split costs ~10 us (device-scope release / acquire around the ticket): it pays from ~32
-// K-steps up; a slice costs ~0.9 us per K-step, the reducing workgroup ~0.36 us per slice: ks ~ sqrt(2.5 * K-steps).
-int auto_ksplit(int M, int N, int K, int pieces, int epi) {
-  int bm, bn;
-  if (pieces == 3) {
-    bm = 64; bn = epi == SOPRO_EPI_GLU ? 128 : 64;
-  } else if (pieces == 1) {
-    const bool small = N <= 64 || M <= 64 || (int64_t)((M + 127) / 128) * ((N + 127) / 128) < 256;
-    if (small) { bm = 64; bn = epi == SOPRO_EPI_GLU ? 128 : 64; } else { bm = bn = 128; }
-  } else {
-    if (N <= 64 || M <= 64) bm = bn = 64; else bm = bn = 128;
-  }
-  const int64_t tiles = (int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const int kt = (K + 31) / 32;
-  if (tiles >= 96 || kt < 32 || tiles > SPLITK_TICKETS) return 1;
-  int ks = (int)lrint(sqrt(2.5 * kt));
-  if (ks > 16) ks = 16;
-  if (ks > 512 / (int)tiles) ks = 512 / (int)tiles;
-  if (ks < 1) ks = 1;
-  while (ks > 1 && (size_t)ks * tiles * bm * bn * 4 > SPLITK_WS_BYTES) --ks;
-  return ks;
-}
-
 struct G {  // one contraction: mirrors sopro_amd.hip.gemm's keyword arguments
   int M = 0, N = 0, K = 0;
   int64_t lda = -1, ldc = -1, ldr = -1, ldw = -1;
@@ -332,9 +308,8 @@ int gemm(hipStream_t s, const float* A, const Wt& w, const float* w_f32_override
     x.rope_rows_per_seg = o.rope_rps;
     x.ln_stats = o.ln_stats; x.ln_stats_out = o.ln_stats_out;
     if (o.ln_stats) x.rms_eps = o.ln_eps;
-    static const bool no_splitk = getenv("SOPRO_NO_SPLITK") && getenv("SOPRO_NO_SPLITK")[0] == '1';  // developer switch
-    if (!no_splitk && o.sk && o.sk->ws && o.rms_eps <= 0.f && o.c_mode != 5) {
-      const int ks = auto_ksplit(o.M, o.N, o.K, w.f16 ? 3 : w.pieces, o.epi);
+    if (o.sk && o.sk->ws && o.rms_eps <= 0.f && o.c_mode != 5) {
+      const int ks = sopro_gemm_auto_ksplit(o.M, o.N, o.K, w.pieces, w.f16, o.epi, (int64_t)SPLITK_WS_BYTES, SPLITK_TICKETS);
       if (ks > 1) {
         x.ksplit = ks; x.n_tickets = SPLITK_TICKETS; x.ws = o.sk->ws; x.ws_bytes = (int64_t)SPLITK_WS_BYTES; x.tickets = o.sk->tickets;
       }

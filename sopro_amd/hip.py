@@ -18,7 +18,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsopro_hip.so")
-ABI_VERSION = 42
+ABI_VERSION = 43
 # Host-side A/B switches whose decision is on record (profiles/rNN_experiments.md) are read from the environment only in DEVELOPER
 # mode (SOPRO_DEV=1) - round 6 housekeeping, the Python twin of the library's `make DEV=1`: a product process ignores them.
 DEV_MODE = os.environ.get("SOPRO_DEV", "0") == "1"
@@ -168,6 +168,7 @@ SYMBOLS = {
     "sopro_packed_w_rows_bytes": (C.c_int64, [_i32, _i32]),
     "sopro_pack_w_rows_bf16": (C.c_int, [_p, _i64, _i32, _i32, _p, _p]),
     "sopro_gemm_8p_takes": (C.c_int, [_p, _p]),
+    "sopro_gemm_auto_ksplit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "sopro_gemm_bf16x3_8p": (C.c_int, [_p, _p, _p, _p]),
     "sopro_gemm_bf16_set_tile_override": (C.c_int, [C.c_int]),
     "sopro_gemm_set_group_m": (C.c_int, [C.c_int]),
@@ -484,7 +485,7 @@ def gemm(A: torch.Tensor, W, Cout: torch.Tensor, *, M: int, N: int, K: int, lda:
             if ks > 1 and (ks * t64 * 64 * 64 * 4 > _SPLITK_WS_BYTES or t64 > _SPLITK_TICKETS):
                 raise SoproHipError(f"ksplit={ks}: {M} x {N} does not fit the split-K workspace / tickets of a stream")
         else:
-            ks = _auto_ksplit(M, N, K, 3 if W.f16 else W.pieces, epilogue) if (dbg is None and _splitk_enabled and rms_eps <= 0.0) else 1
+            ks = _auto_ksplit(M, N, K, W.pieces, epilogue, W.f16) if (dbg is None and _splitk_enabled and rms_eps <= 0.0) else 1
         if ks > 1 or ksplit is not None:
             ws, tk = _splitk_buffers()
             x.ksplit, x.n_tickets, x.ws, x.ws_bytes, x.tickets = ks, int(tk.numel()), ptr(ws), int(ws.numel()) * 4, ptr(tk, torch.int32)
@@ -537,32 +538,16 @@ def gemm(A: torch.Tensor, W, Cout: torch.Tensor, *, M: int, N: int, K: int, lda:
         _prof.end(fam, 2.0 * M * N * K, e0)
 
 
-_splitk_enabled = os.environ.get("SOPRO_NO_SPLITK", "0") != "1"
+_splitk_enabled = True  # (SOPRO_NO_SPLITK=1 is read by the library's rule; tests toggle this)
 _splitk_pool: dict = {}  # stream handle -> (workspace, tickets): split-K scratch belongs to one stream at a time
 _SPLITK_WS_BYTES = 32 << 20
 _SPLITK_TICKETS = 1024
 
 
-def _auto_ksplit(M: int, N: int, K: int, pieces: int, epilogue: int) -> int:
-    """K slices for a problem with too few output tiles to occupy the chip (streaming chunks, batch 1): its K loop
-    would otherwise run at one memory latency per 32-wide step on a handful of workgroups."""
-    if pieces == 3:
-        bm, bn = (64, 128) if epilogue == EPI_GLU else (64, 64)
-    elif pieces == 1:  # sopro_gemm_bf16x1's tile rule
-        small = N <= 64 or M <= 64 or (-(-M // 128) * -(-N // 128)) < 256
-        bm, bn = ((64, 128) if epilogue == EPI_GLU else (64, 64)) if small else (128, 128)
-    else:
-        bm, bn = (64, 64) if (N <= 64 or M <= 64) else (128, 128)
-    tiles = -(-M // bm) * -(-N // bn)
-    kt = -(-K // 32)
-    # the split costs ~10 us (device-scope release / acquire around the ticket): it pays from ~32 K-steps (K >= 1024) up
-    if tiles >= 96 or kt < 32 or tiles > _SPLITK_TICKETS:
-        return 1
-    # a slice costs ~0.9 us per K-step, the reducing workgroup ~0.36 us per slice of a 64x64 tile: ks ~ sqrt(2.5 * kt)
-    ks = max(1, min(16, int(round((2.5 * kt) ** 0.5)), 512 // tiles))
-    while ks > 1 and ks * tiles * bm * bn * 4 > _SPLITK_WS_BYTES:
-        ks -= 1
-    return ks
+def _auto_ksplit(M: int, N: int, K: int, pieces: int, epilogue: int, f16: bool = False) -> int:
+    """K slices for a problem with too few output tiles to occupy the chip (streaming chunks, batch 1): the library's rule
+    (sopro_gemm_auto_ksplit, which the stage sequences ask too) for this host's per-stream scratch."""
+    return load().sopro_gemm_auto_ksplit(M, N, K, pieces, int(f16), epilogue, _SPLITK_WS_BYTES, _SPLITK_TICKETS)
 
 
 def _splitk_buffers():

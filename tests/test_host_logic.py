@@ -22,6 +22,45 @@ def test_auto_ksplit_only_for_few_tiles_and_long_k():
         assert 1 <= ks <= 16 and ks * tiles * bm * bn * 4 <= hip._SPLITK_WS_BYTES and tiles <= hip._SPLITK_TICKETS
 
 
+NONE, GELU, GLU, RES = hip.EPI_NONE, hip.EPI_GELU, hip.EPI_GLU, hip.EPI_RES
+# (M, N, K, pieces, f16, epilogue) -> K slices, recorded from the two host copies of the rule (Python and stage sequences, which agreed
+# on all of these) before they became the library's one: both sides of every threshold.
+AUTO_KSPLIT = [
+    # 96 tiles: 128 x 128 (three-pass), 64 x 64 (six-pass)
+    (2944, 512, 2048, 2, 0, NONE, 5), (2945, 512, 2048, 2, 0, NONE, 1), (960, 384, 1536, 3, 0, RES, 5), (961, 384, 1536, 3, 0, RES, 1),
+    # K = 1024
+    (12, 512, 992, 2, 0, RES, 1), (12, 512, 1024, 2, 0, RES, 9), (6, 384, 992, 3, 0, NONE, 1), (6, 384, 1024, 3, 0, NONE, 9),
+    # M = 64 / 65 and N = 64 / 65: 64 x 64 tiles against 128 x 128 (three-pass), against many small ones (one-pass below its 256-tile cut)
+    (64, 4096, 2048, 2, 0, NONE, 8), (65, 4096, 2048, 2, 0, NONE, 13), (4096, 64, 2048, 2, 0, NONE, 8), (4096, 65, 2048, 2, 0, NONE, 13),
+    (64, 4096, 2048, 1, 0, NONE, 8), (65, 4096, 2048, 1, 0, NONE, 1), (4096, 64, 2048, 1, 0, GELU, 8), (4096, 65, 2048, 1, 0, GELU, 1),
+    # one-pass: 248 / 256 tiles of 128 x 128 (small tiles below, 128 x 128 from there: enough tiles either way), and problems that split
+    (3968, 1024, 2048, 1, 0, NONE, 1), (4096, 1024, 2048, 1, 0, NONE, 1), (1000, 768, 2048, 1, 0, NONE, 1),
+    (1000, 384, 2048, 1, 0, GLU, 10), (1000, 512, 2048, 1, 0, GLU, 8), (12, 512, 2048, 1, 0, GLU, 13), (12, 512, 2048, 1, 0, NONE, 13),
+    # f16 three-pass: the six-pass family's small tiles; no split from M = 8192, where it launches 128 x 128 tiles
+    (8191, 128, 1024, 2, 1, NONE, 1), (8192, 128, 1024, 2, 1, NONE, 1), (8192, 64, 2048, 2, 1, NONE, 1), (12160, 128, 1024, 2, 1, NONE, 1),
+    (12161, 128, 1024, 2, 1, NONE, 1), (8192, 64, 2048, 3, 0, NONE, 1), (300, 128, 1024, 2, 1, GELU, 9),
+    # GLU: 64 x 128 tiles
+    (300, 768, 2048, 3, 0, NONE, 8), (300, 768, 2048, 3, 0, GLU, 13), (300, 768, 2048, 2, 1, GLU, 13), (6, 768, 1536, 3, 0, GLU, 11),
+    # the caps: 16 slices, 512 workgroups
+    (200, 384, 1536, 3, 0, RES, 11), (200, 384, 4096, 2, 0, RES, 16), (1, 32, 8192, 2, 0, NONE, 16), (1, 32768, 8192, 2, 0, NONE, 1),
+    (256, 2048, 8192, 2, 0, NONE, 16), (1000, 256, 4096, 2, 0, GELU, 16), (1000, 256, 4096, 3, 0, GELU, 8),
+    # whole batches
+    (6144, 384, 1536, 2, 0, NONE, 1), (12800, 1536, 512, 2, 0, NONE, 1), (25600, 32768, 1024, 1, 0, NONE, 1),
+]
+
+
+def test_auto_ksplit_table():
+    """The rule the product runs (sopro_gemm_auto_ksplit, asked with the Python host's scratch sizes) against recorded decisions; and
+    hip._auto_ksplit, through which the tests above and the GPU tests ask, is that rule (the f16 family as `pieces` 3 or by its flag)."""
+    lib = hip.load()
+    for (M, N, K, pieces, f16, epi, ks) in AUTO_KSPLIT:
+        assert lib.sopro_gemm_auto_ksplit(M, N, K, pieces, f16, epi, hip._SPLITK_WS_BYTES, hip._SPLITK_TICKETS) == ks, (M, N, K, pieces, f16, epi)
+        assert hip._auto_ksplit(M, N, K, 3 if f16 else pieces, epi) == ks and hip._auto_ksplit(M, N, K, pieces, epi, bool(f16)) == ks
+    # the caller's scratch bounds the answer: fewer tickets than tiles, or room for fewer slices
+    assert lib.sopro_gemm_auto_ksplit(12, 512, 2048, 2, 0, NONE, hip._SPLITK_WS_BYTES, 1) == 1
+    assert lib.sopro_gemm_auto_ksplit(12, 512, 2048, 2, 0, NONE, 5 * 8 * 64 * 64 * 4, hip._SPLITK_TICKETS) == 5
+
+
 def test_workspace_keeps_one_buffer_per_shape_and_counts_bytes():
     ws = Workspace(torch.device("cpu"))
     a = ws.get("x", (4, 8))

@@ -216,7 +216,7 @@ def test_library_helpers_agree_with_the_host_arithmetic():
     assert lib.sopro_pitch_chunk_out_cap(-1) == -1
     assert lib.sopro_pitch_rows_f32(None, 0, None, 0, None, None, None, 1, 1, None, 1, None, 0, 0, None, None) == -2
     assert b"non-NULL" in lib.sopro_last_error()
-    assert hip.PITCH_TILE == 2048 and hip.ABI_VERSION == 42
+    assert hip.PITCH_TILE == 2048 and hip.ABI_VERSION == 43
 
 
 def test_pitch_is_keyword_only_with_default_zero_everywhere():

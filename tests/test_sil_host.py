@@ -269,7 +269,7 @@ def test_library_helpers_and_argument_checks():
     calls = hip.sil_calls
     for name in ("sopro_sil_state_bytes", "sopro_sil_chunk_out_cap", "sopro_sil_ws_bytes", "sopro_sil_rows_f32"):
         assert name in hip.SYMBOLS
-    assert (hip.SIL_HOP, hip.SIL_TAIL, hip.SIL_TILE, hip.SIL_PLAN_WORDS) == (240, 4608, 2048, 64) and hip.ABI_VERSION == 42
+    assert (hip.SIL_HOP, hip.SIL_TAIL, hip.SIL_TILE, hip.SIL_PLAN_WORDS) == (240, 4608, 2048, 64) and hip.ABI_VERSION == 43
     assert hip.SIL_TAIL >= 18 * 240 + 239                                # the held hop, a ring of b + 1 <= 17, the incomplete hop
     assert lib.sopro_sil_state_bytes(0) == 0 and lib.sopro_sil_state_bytes(2) == 2 * lib.sopro_sil_state_bytes(1) >= 2 * (6 * 8 + 4608 * 4)
     for n in (0, 1, 1920, 11520):

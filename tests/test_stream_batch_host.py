@@ -40,7 +40,7 @@ def test_batch_state_layout_matches_the_header(tmp_path):
     for f in fields:
         assert int(got[f]) == getattr(hip.MimiStreamBatch, f).offset, f
     assert int(got["max"]) == 64
-    assert hip.ABI_VERSION == 42 and hip.load().sopro_abi_version() == 42
+    assert hip.ABI_VERSION == 43 and hip.load().sopro_abi_version() == 43
 
 
 def test_batch_kv_bytes(cpu_engine):

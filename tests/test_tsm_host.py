@@ -130,7 +130,7 @@ def test_library_helpers_agree_with_the_host_arithmetic():
     assert lib.sopro_tsm_chunk_out_cap(0) >= (1920 // 240 + 2) * 480 and lib.sopro_tsm_chunk_out_cap(11520) >= (11520 + 1920) // 240 * 480
     assert lib.sopro_tsm_rows_f32(None, 0, None, 0, None, 1, None, 1, None, None, 0, 0, None, None, 0, None) == -2
     assert b"non-NULL" in lib.sopro_last_error()
-    assert hip.ABI_VERSION == 42
+    assert hip.ABI_VERSION == 43
 
 
 def test_speed_is_keyword_only_with_default_one_everywhere():

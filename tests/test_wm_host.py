@@ -251,5 +251,5 @@ def test_library_helpers_and_argument_checks():
     assert b"non-NULL" in lib.sopro_last_error()
     assert lib.sopro_wm_corr_rows_f32(None, None, 1, None, 1, None, None) == -2
     assert lib.sopro_wm_peak_rows_f32(None, 1, None, None) == -2
-    assert (hip.WM_HS, hip.WM_P, hip.WM_TAIL) == (480, 8192, 1536) and hip.WM_TILE % hip.WM_HS == 0 and hip.ABI_VERSION == 42
+    assert (hip.WM_HS, hip.WM_P, hip.WM_TAIL) == (480, 8192, 1536) and hip.WM_TILE % hip.WM_HS == 0 and hip.ABI_VERSION == 43
     assert hip.wm_calls() == 0  # nothing here launched anything

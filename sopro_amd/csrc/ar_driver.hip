@@ -90,15 +90,6 @@ __device__ __forceinline__ unsigned wave_nth_largest_u32(unsigned v, int n) {
   return r;
 }
 
-// Lanes of ONE wave exchanging data through LDS: the hardware executes a wave's LDS operations in issue order, so no barrier
-// is needed - but the compiler reasons per thread (it may forward a thread's own store to its later load, or move a load into
-// a branch).  A wavefront-scope fence pair + a scheduling barrier pins the order; it emits no instruction beyond a wait.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr int RECENT = 64;   // rolling token window per row: slot j = token sampled j+1 frames ago (-1 = none)
 constexpr int PER = 9;       // logits per thread: ceil(2049 / 256), element q*256 + tid
 constexpr int WREG = PER * 64;             // candidate slots of one wave's region (every logit of the wave may qualify)

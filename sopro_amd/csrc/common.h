@@ -173,6 +173,15 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Lanes of ONE wave exchanging data through LDS: the hardware executes a wave's LDS operations in issue order, so no barrier
+// is needed - but the compiler reasons per thread (it may forward a thread's own store to its later load, or move a load into
+// a branch).  A wavefront-scope fence pair + a scheduling barrier pins the order; it emits no instruction beyond a wait.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // library-side launch timing (prof.hip): a scope around one heavy launch of a stage sequence; a no-op unless sopro_prof_enable(1)
 struct sopro_prof_scope {
   void* rec;

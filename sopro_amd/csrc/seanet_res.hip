@@ -15,7 +15,10 @@
 // lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  ELU(h) is activated and split once per
 // element while the tile is staged (LDS row = [128 hi | 128 lo] + 16 B pad = 528 B: the k=3 window of a row is three
 // consecutive LDS rows and the 16-lane ds_read_b128 fragment reads are conflict free); the intermediate stays in LDS.
-#include "common.h"
+// The fp32 kernel and the kernel on bf16 rows differ in how a tile is staged and stored; what both do in between - the weight
+// fragments, the first convolution's walk (ws_walk of seanet_mma.h), the K-half exchange and the second convolution - is
+// written once, below.
+#include "seanet_mma.h"
 
 namespace {
 
@@ -23,19 +26,70 @@ constexpr int RC = 128;           // channels
 constexpr int RH = 64;            // hidden channels of the block
 constexpr int RTO = 64;           // output rows per tile
 constexpr int RHR = RTO + 2;      // staged rows: samples s0-2 .. s0+RTO-1
-constexpr int REROW = 2 * RC * 2 + 16;   // 528
-constexpr int RYROW = 2 * RH * 2 + 16;   // 272
 
-typedef __bf16 rbf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ rbf16x8 rfrag(const uint4& v) { return *reinterpret_cast<const rbf16x8*>(&v); }
+// ---- the pieces both kernels share.  EROW / YROW: row pitches of the staged tile and of the intermediate (split form with
+// the lo planes 2 * RC / 2 * RH bytes behind the hi planes, or bf16 rows: PASSES == 1 reads and writes the hi planes only).
 
-__device__ __forceinline__ void rsplit8(const float* __restrict__ p, uint4& hi, uint4& lo) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  split2_bf16(a.x, a.y, hi.x, lo.x);
-  split2_bf16(a.z, a.w, hi.y, lo.y);
-  split2_bf16(b.x, b.y, hi.z, lo.z);
-  split2_bf16(b.z, b.w, hi.w, lo.w);
+// weights as (hi, lo) B fragments, once per workgroup: n = lane & 31, k = 16 * substep + 8 * (lane >> 5) .. + 7
+// (a one-pass kernel hands the hi arrays in for the lo arrays: split_wfrags of seanet_mma.h)
+template <int PASSES, int NL1, int NL2>
+__device__ __forceinline__ void res_weights(const float* __restrict__ w1, const float* __restrict__ w2, int wave, int frow, int fg, uint4 (&w1h)[12],
+                                            uint4 (&w1l)[NL1], uint4 (&w2h)[4], uint4 (&w2l)[NL2]) {
+  const int nt1 = wave & 1, kh = wave >> 1;
+  split_wfrags<PASSES>(w1 + (int64_t)(nt1 * 32 + frow) * (3 * RC) + kh * 12 * 16 + fg * 8, w1h, w1l);
+  split_wfrags<PASSES>(w2 + (int64_t)(wave * 32 + frow) * RH + fg * 8, w2h, w2l);
 }
+
+// conv k=3, 128 -> 64: intermediate row m (sample s0+m) reads staged rows m, m+1, m+2; wave (nt1, kh) = columns 32 nt1 .. of the
+// K half kh (substeps 12 kh .. 12 kh + 11 of the 24).  The two K halves of a block then meet through LDS: wave (nt, kh) keeps
+// row tile kh and hands row tile 1-kh to wave (nt, 1-kh) through `red` (the end of res_conv1); behind a workgroup barrier
+// res_take_over adds in a fixed order (K half 0 first, whichever wave adds), applies bias and ELU and writes the split
+// intermediate to `ys`.
+template <int PASSES, int EROW, int NL>
+__device__ __forceinline__ void res_conv1(const unsigned char* es, int wave, int lane, const uint4 (&w1h)[12], const uint4 (&w1l)[NL], float* red,
+                                          f32x16 (&acc)[2]) {
+  const int kh = wave >> 1;
+  ws_walk<PASSES, 12, EROW, 2 * RC>(es + (lane & 31) * EROW + (lane >> 5) * 16, kh * 12, w1h, w1l, acc);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = kh ? acc[0][r] : acc[1][r];
+}
+template <int PASSES, int YROW>
+__device__ __forceinline__ void res_take_over(const float* red, const f32x16 (&acc)[2], float b1v, int wave, int lane, unsigned char* ys) {
+  const int frow = lane & 31, fg = lane >> 5, nt1 = wave & 1, kh = wave >> 1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float mine = kh ? acc[1][r] : acc[0][r];
+    const float other = red[((wave ^ 2) * 16 + r) * 64 + lane];
+    const float v = (kh ? other + mine : mine + other) + b1v;
+    const int mr = kh * 32 + acc32_row(r) + 4 * fg;
+    unsigned hi, lo;
+    split2_bf16(eluf_(v), 0.f, hi, lo);
+    *reinterpret_cast<unsigned short*>(ys + mr * YROW + (nt1 * 32 + frow) * 2) = (unsigned short)(hi & 0xffffu);
+    if (PASSES == 3) *reinterpret_cast<unsigned short*>(ys + mr * YROW + 2 * RH + (nt1 * 32 + frow) * 2) = (unsigned short)(lo & 0xffffu);
+  }
+}
+
+// conv k=1, 64 -> 128 on row tile mt of the intermediate: wave w = output columns 32 w ..
+template <int PASSES, int YROW, int NL>
+__device__ __forceinline__ f32x16 res_conv2(const unsigned char* ys, int mt, int lane, const uint4 (&w2h)[4], const uint4 (&w2l)[NL]) {
+  f32x16 acc2;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+  const unsigned char* a = ys + (mt * 32 + (lane & 31)) * YROW + (lane >> 5) * 16;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const uint4 ah = *reinterpret_cast<const uint4*>(a + s * 32);
+    if (PASSES == 3) {
+      const uint4 al = *reinterpret_cast<const uint4*>(a + 2 * RH + s * 32);
+      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(al), frag(w2h[s]), acc2, 0, 0, 0);
+      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(ah), frag(w2l[s]), acc2, 0, 0, 0);
+    }
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(ah), frag(w2h[s]), acc2, 0, 0, 0);
+  }
+  return acc2;
+}
+
+constexpr int REROW = split_row_bytes(RC), RYROW = split_row_bytes(RH);  // the fp32 kernel's tiles: 528, 272
 
 // Round 6: the NEXT tile's raw rows are brought into LDS by LDS-DMA (global_load_lds_dwordx4) while the current tile's second half runs:
 // the split-ELU tile `es` is dead from the barrier behind the first convolution until the next tile is staged, so the raw fp32 rows of
@@ -75,17 +129,12 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_kernel(const float* __re
   const int b = blockIdx.y;
   const bool big = (int64_t)gridDim.y * T * 128 * 4 >= SOPRO_BIG_BYTES;  // a large output: stored with the non-temporal hint (common.h)
   const int frow = lane & 31, fg = lane >> 5;
-  const int nt1 = wave & 1, kh = wave >> 1;
+  const int nt1 = wave & 1;
   const float* hb = h + (int64_t)b * h_seg_stride;   // 2 zero rows, then T rows of RC floats
   float* ob = out + (int64_t)b * out_seg_stride;     // same layout
 
-  // ---- weights as (hi, lo) B fragments, once per workgroup: n = lane & 31, k = 16 * substep + 8 * (lane >> 5) .. + 7
-  uint4 w1h[12], w1l[12];
-#pragma unroll
-  for (int s = 0; s < 12; ++s) rsplit8(w1 + (int64_t)(nt1 * 32 + frow) * (3 * RC) + (kh * 12 + s) * 16 + fg * 8, w1h[s], w1l[s]);
-  uint4 w2h[4], w2l[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) rsplit8(w2 + (int64_t)(wave * 32 + frow) * RH + s * 16 + fg * 8, w2h[s], w2l[s]);
+  uint4 w1h[12], w1l[PASSES == 3 ? 12 : 1], w2h[4], w2l[PASSES == 3 ? 4 : 1];
+  res_weights<PASSES>(w1, w2, wave, frow, fg, w1h, w1l, w2h, w2l);
   const float b1v = b1[nt1 * 32 + frow];
   const float b2v = b2[wave * 32 + frow];
 
@@ -133,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_kernel(const float* __re
     float skip0[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      skip0[r] = *reinterpret_cast<const float*>(es + ((r & 3) + 8 * (r >> 2) + 4 * fg + 2) * (RC * 4) + (wave * 32 + frow) * 4);
+      skip0[r] = *reinterpret_cast<const float*>(es + (acc32_row(r) + 4 * fg + 2) * (RC * 4) + (wave * 32 + frow) * 4);
     __syncthreads();                 // every thread holds its pieces before the split image overwrites the raw one
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
@@ -149,101 +198,28 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_kernel(const float* __re
     }
     __syncthreads();
 
-    // ---- conv k=3, 128 -> 64: intermediate row m (sample s0+m) reads staged rows m, m+1, m+2.
-    // K index = tap * 128 + channel; substep s covers tap s / 8, channels 16 * (s % 8) .. + 15
+    // ---- conv k=3, 128 -> 64, and this wave's half of the K-half exchange
     f32x16 acc[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-    }
-    {
-      // both row tiles advance together (two independent accumulator chains) and the fragment reads run DEPTH substeps ahead
-      // of the MFMAs that consume them (left to itself the compiler emits read -> wait -> MFMA per substep: every LDS latency
-      // exposed); the scheduling barriers pin that order
-      constexpr int DEPTH = 2;
-      const unsigned char* a = es + frow * REROW + fg * 16;
-      auto fptr = [&](int s, int mt) { const int sg = kh * 12 + s; return a + mt * 32 * REROW + (sg >> 3) * REROW + (sg & 7) * 32; };
-      uint4 ah[DEPTH][2], al[DEPTH][2];
-#pragma unroll
-      for (int s = 0; s < DEPTH; ++s)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-          ah[s][mt] = *reinterpret_cast<const uint4*>(fptr(s, mt));
-          al[s][mt] = PASSES == 3 ? *reinterpret_cast<const uint4*>(fptr(s, mt) + 2 * RC) : ah[s][mt];
-        }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 12; ++s) {
-        uint4 ch[2], cl[2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) { ch[mt] = ah[s % DEPTH][mt]; cl[mt] = al[s % DEPTH][mt]; }
-        if (PASSES == 3) {
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(cl[mt]), rfrag(w1h[s]), acc[mt], 0, 0, 0);
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(ch[mt]), rfrag(w1l[s]), acc[mt], 0, 0, 0);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(ch[mt]), rfrag(w1h[s]), acc[mt], 0, 0, 0);
-        if (s + DEPTH < 12) {
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) {
-            ah[s % DEPTH][mt] = *reinterpret_cast<const uint4*>(fptr(s + DEPTH, mt));
-            al[s % DEPTH][mt] = PASSES == 3 ? *reinterpret_cast<const uint4*>(fptr(s + DEPTH, mt) + 2 * RC) : ah[s % DEPTH][mt];
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // the two K halves of a block meet through LDS: wave (nt, kh) keeps row tile kh and hands row tile 1-kh to wave (nt, 1-kh)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = kh ? acc[0][r] : acc[1][r];
+    res_conv1<PASSES, REROW>(es, wave, lane, w1h, w1l, red, acc);
     __syncthreads();
     // Addresses of the tile's output / skip elements: (utterance base, wave-uniform) + a 32-bit byte offset = this lane's place in the
     // tile's first row group + a compile-time row term - no 64-bit arithmetic, and for whole tiles (all but an utterance's last) no
     // per-element bounds test either (the per-store compare + branch + address pair were ~10 instructions per element)
     const bool whole = s0 + RTO <= T;  // uniform
     const unsigned lane_off = (unsigned)(((s0 + 2 + 4 * fg) * RC + wave * 32 + frow) * 4);
-    auto row_off = [&](int mt, int r) { return lane_off + (unsigned)((mt * 32 + (r & 3) + 8 * (r >> 2)) * RC * 4); };
-    auto row_ok = [&](int mt, int r) { return whole || s0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg < T; };
+    auto row_off = [&](int mt, int r) { return lane_off + (unsigned)((mt * 32 + acc32_row(r)) * RC * 4); };
+    auto row_ok = [&](int mt, int r) { return whole || s0 + mt * 32 + acc32_row(r) + 4 * fg < T; };
     const unsigned last_off = (unsigned)(((T + 1) * RC + wave * 32 + frow) * 4);  // rows past the end are never stored: read the last padded row
     // ---- es is dead until the next tile is staged: its raw rows start their way now, under the exchange and the second convolution
     // (also past the last tile - rows past the end read the zero row; the loop top / the kernel's end wait for them)
     request(s0 + RTO);
-    {
-      const int mt = kh;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float mine = kh ? acc[1][r] : acc[0][r];
-        const float other = red[((wave ^ 2) * 16 + r) * 64 + lane];
-        const float v = (kh ? other + mine : mine + other) + b1v;   // K half 0 first, whichever wave adds
-        const int mr = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg;
-        unsigned hi, lo;
-        split2_bf16(eluf_(v), 0.f, hi, lo);
-        *reinterpret_cast<unsigned short*>(ys + mr * RYROW + (nt1 * 32 + frow) * 2) = (unsigned short)(hi & 0xffffu);
-        if (PASSES == 3) *reinterpret_cast<unsigned short*>(ys + mr * RYROW + 2 * RH + (nt1 * 32 + frow) * 2) = (unsigned short)(lo & 0xffffu);
-      }
-    }
+    res_take_over<PASSES, RYROW>(red, acc, b1v, wave, lane, ys);
     lds_barrier();
 
     // ---- conv k=1, 64 -> 128 (wave w: output columns 32w ..) + skip, ELU, store
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
-      f32x16 acc2;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
-      const unsigned char* a = ys + (mt * 32 + frow) * RYROW + fg * 16;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const uint4 ah = *reinterpret_cast<const uint4*>(a + s * 32);
-        if (PASSES == 3) {
-          const uint4 al = *reinterpret_cast<const uint4*>(a + 2 * RH + s * 32);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(al), rfrag(w2h[s]), acc2, 0, 0, 0);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(ah), rfrag(w2l[s]), acc2, 0, 0, 0);
-        }
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(ah), rfrag(w2h[s]), acc2, 0, 0, 0);
-      }
+      const f32x16 acc2 = res_conv2<PASSES, RYROW>(ys, mt, lane, w2h, w2l);
       float skip[16];
       if (mt == 0) {
 #pragma unroll
@@ -271,8 +247,7 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_kernel(const float* __re
 // at half the bytes; one MFMA pass on the rounded operands.  ELU is applied to the widened values and the result is rounded again
 // while the tile is staged (LDS row = 128 bf16 + 16 B pad = 272 B); the skip operand is the raw bf16 h widened to fp32; the sum is
 // accumulated in fp32 and rounded once when it is stored (two neighbouring columns per lane: 4-byte stores).
-constexpr int REROW_H = RC * 2 + 16;   // 272
-constexpr int RYROW_H = RH * 2 + 16;   // 144
+constexpr int REROW_H = bf16_row_bytes(RC), RYROW_H = bf16_row_bytes(RH);  // 272, 144
 __device__ __forceinline__ unsigned relu2_bf16(unsigned pk) {  // two packed bf16 -> ELU in fp32 -> two packed bf16
   unsigned o, lo_;
   split2_bf16(eluf_(__uint_as_float(pk << 16)), eluf_(__uint_as_float(pk & 0xffff0000u)), o, lo_);
@@ -289,16 +264,12 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_hb_kernel(const unsigned
   const int b = blockIdx.y;
   const bool big = (int64_t)gridDim.y * T * 128 * 2 >= SOPRO_BIG_BYTES;
   const int frow = lane & 31, fg = lane >> 5;
-  const int nt1 = wave & 1, kh = wave >> 1;
+  const int nt1 = wave & 1;
   const unsigned short* hb = h + (int64_t)b * h_seg_stride;   // 2 zero rows, then T rows of RC bf16
   unsigned short* ob = out + (int64_t)b * out_seg_stride;
 
-  uint4 w1h[12];
-#pragma unroll
-  for (int s = 0; s < 12; ++s) { uint4 lo; rsplit8(w1 + (int64_t)(nt1 * 32 + frow) * (3 * RC) + (kh * 12 + s) * 16 + fg * 8, w1h[s], lo); }
-  uint4 w2h[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) { uint4 lo; rsplit8(w2 + (int64_t)(wave * 32 + frow) * RH + s * 16 + fg * 8, w2h[s], lo); }
+  uint4 w1h[12], w2h[4];  // one pass: hi fragments only
+  res_weights<1>(w1, w2, wave, frow, fg, w1h, w1h, w2h, w2h);
   const float b1v = b1[nt1 * 32 + frow];
   const float b2v = b2[wave * 32 + frow];
 
@@ -326,55 +297,14 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_hb_kernel(const unsigned
     }
     __syncthreads();
 
+    // ---- conv k=3, 128 -> 64, the K-half exchange, the bf16 intermediate
     f32x16 acc[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-    }
-    {
-      constexpr int DEPTH = 2;
-      const unsigned char* a = es + frow * REROW_H + fg * 16;
-      auto fptr = [&](int s, int mt) { const int sg = kh * 12 + s; return a + mt * 32 * REROW_H + (sg >> 3) * REROW_H + (sg & 7) * 32; };
-      uint4 ah[DEPTH][2];
-#pragma unroll
-      for (int s = 0; s < DEPTH; ++s)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) ah[s][mt] = *reinterpret_cast<const uint4*>(fptr(s, mt));
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 12; ++s) {
-        uint4 ch[2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) ch[mt] = ah[s % DEPTH][mt];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(ch[mt]), rfrag(w1h[s]), acc[mt], 0, 0, 0);
-        if (s + DEPTH < 12) {
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) ah[s % DEPTH][mt] = *reinterpret_cast<const uint4*>(fptr(s + DEPTH, mt));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = kh ? acc[0][r] : acc[1][r];
+    res_conv1<1, REROW_H>(es, wave, lane, w1h, w1h, red, acc);
     __syncthreads();
-    {
-      const int mt = kh;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float mine = kh ? acc[1][r] : acc[0][r];
-        const float other = red[((wave ^ 2) * 16 + r) * 64 + lane];
-        const float v1 = (kh ? other + mine : mine + other) + b1v;   // K half 0 first, whichever wave adds
-        const int mr = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg;
-        unsigned hi, lo;
-        split2_bf16(eluf_(v1), 0.f, hi, lo);
-        *reinterpret_cast<unsigned short*>(ys + mr * RYROW_H + (nt1 * 32 + frow) * 2) = (unsigned short)(hi & 0xffffu);
-      }
-    }
+    res_take_over<1, RYROW_H>(red, acc, b1v, wave, lane, ys);
     __syncthreads();
 
-    // ---- conv k=1, 64 -> 128 (wave w: output columns 32w ..) + skip, ELU, store (column pairs: see seanet_up128_hb_kernel)
+    // ---- conv k=1, 64 -> 128 (wave w: output columns 32w ..) + skip, ELU, store (column pairs: pair_cols of seanet_mma.h)
     const bool odd = (lane & 1) != 0;
     const int colp = wave * 32 + (frow & ~1);
 #pragma unroll
@@ -384,29 +314,19 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_hb_kernel(const unsigned
       // the compare + branch + 64-bit address pair per element were a third of this epilogue's instructions)
       const bool whole = s0 + RTO <= T;  // uniform
       const unsigned lane_off = (unsigned)(((s0 + 2 + 4 * fg + (odd ? 1 : 0)) * RC + colp) * 2);
-      auto row_off = [&](int r) { return lane_off + (unsigned)((mt * 32 + (r & 3) + 8 * (r >> 2)) * RC * 2); };
-      auto row_ok = [&](int r) { return whole || s0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg + (odd ? 1 : 0) < T; };
+      auto row_off = [&](int r) { return lane_off + (unsigned)((mt * 32 + acc32_row(r)) * RC * 2); };
+      auto row_ok = [&](int r) { return whole || s0 + mt * 32 + acc32_row(r) + 4 * fg + (odd ? 1 : 0) < T; };
       const unsigned last_off = (unsigned)(((T + 1) * RC + colp) * 2);  // rows past the end are never stored: read the last padded row
       unsigned skip[8];
 #pragma unroll
       for (int r = 0; r < 16; r += 2)
         skip[r >> 1] = *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(hb) + (row_ok(r) ? row_off(r) : last_off));
-      f32x16 acc2;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
-      const unsigned char* a = ys + (mt * 32 + frow) * RYROW_H + fg * 16;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const uint4 ah = *reinterpret_cast<const uint4*>(a + s * 32);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rfrag(ah), rfrag(w2h[s]), acc2, 0, 0, 0);
-      }
+      const f32x16 acc2 = res_conv2<1, RYROW_H>(ys, mt, lane, w2h, w2h);
       unsigned pkv[8];
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        const float mine0 = acc2[r] + b2v, mine1 = acc2[r + 1] + b2v;
-        // (the neighbour column's bias travels with its value: mine* already hold it)
-        const float got = __shfl_xor(odd ? mine0 : mine1, 1, 64);
-        const float c0 = odd ? got : mine0, c1 = odd ? mine1 : got;
+        float c0, c1;
+        pair_cols(acc2[r] + b2v, acc2[r + 1] + b2v, odd, c0, c1);  // (the neighbour column's bias travels with its value)
         const unsigned sk = skip[r >> 1];
         unsigned pk, lo_;
         split2_bf16(eluf_(__uint_as_float(sk << 16) + c0), eluf_(__uint_as_float(sk & 0xffff0000u) + c1), pk, lo_);
@@ -424,9 +344,26 @@ __global__ __launch_bounds__(256, 2) void seanet_res128_hb_kernel(const unsigned
   }
 }
 
+int g_res_tiles = 0;  // developer probe / tests: tiles per workgroup, 0 = heuristic
+
+// the weight fragments cost ~1000 VALU instructions per wave: amortised over several tiles once every CU has work anyway
+int res_tiles(int ntile, int B) {
+  const int64_t all = (int64_t)ntile * B;
+  return g_res_tiles > 0 ? g_res_tiles : (all >= 16 * 2048 ? 16 : (all >= 8 * 1024 ? 8 : (all >= 2048 ? 2 : 1)));
+}
+
+// LDS: the dynamic request of the fp32 kernels, 0 for the kernel on bf16 rows (static LDS)
+template <auto KERN, int LDS, class P>
+int launch_res(const P* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2, const float* b2, P* out, int64_t out_seg_stride,
+               int32_t B, int32_t T, hipStream_t s) {
+  const int ntile = (T + RTO - 1) / RTO, tiles = res_tiles(ntile, B);
+  if constexpr (LDS != 0) SOPRO_SET_MAX_LDS_ONCE(KERN, LDS);
+  hipLaunchKernelGGL(KERN, dim3((ntile + tiles - 1) / tiles, B), dim3(256), LDS, s, h, h_seg_stride, w1, b1, w2, b2, out, out_seg_stride, T, tiles);
+  SOPRO_LAUNCH_CHECK();
+}
+
 }  // namespace
 
-static int g_res_tiles = 0;  // developer probe / tests: tiles per workgroup, 0 = heuristic
 extern "C" int sopro_seanet_res_set_tiles(int tiles) {
   g_res_tiles = tiles > 0 ? tiles : 0;
   return 0;
@@ -440,22 +377,10 @@ extern "C" int sopro_seanet_res128_p_f32(const float* h, int64_t h_seg_stride, c
   SOPRO_CHECK_ARG(aligned16(h) && aligned16(w1) && aligned16(w2) && aligned16(out) && (h_seg_stride & 3) == 0 && (out_seg_stride & 3) == 0,
                   "alignment");
   SOPRO_CHECK_ARG(h_seg_stride >= (int64_t)(T + 2) * RC && out_seg_stride >= (int64_t)(T + 2) * RC, "segments hold 2 + T rows of 128 floats");
-  const int ntile = (T + RTO - 1) / RTO;
-  // the weight fragments cost ~1000 VALU instructions per wave: amortised over several tiles once every CU has work anyway
-  const int64_t all = (int64_t)ntile * B;
-  const int tiles = g_res_tiles > 0 ? g_res_tiles : (all >= 16 * 2048 ? 16 : (all >= 8 * 1024 ? 8 : (all >= 2048 ? 2 : 1)));
-  dim3 grid((ntile + tiles - 1) / tiles, B);
   SOPRO_CHECK_ARG(T < (1 << 21), "T must stay below 2^21 rows per utterance (32-bit byte offsets of the skip operand)");
-  if (passes == 3) {
-    auto kern = seanet_res128_kernel<3>;
-    SOPRO_SET_MAX_LDS_ONCE(kern, RES_LDS);
-    hipLaunchKernelGGL(kern, grid, dim3(256), RES_LDS, (hipStream_t)stream, h, h_seg_stride, w1, b1, w2, b2, out, out_seg_stride, T, tiles);
-  } else {  // the engine's bf16 mode: hi * hi only
-    auto kern = seanet_res128_kernel<1>;
-    SOPRO_SET_MAX_LDS_ONCE(kern, RES_LDS);
-    hipLaunchKernelGGL(kern, grid, dim3(256), RES_LDS, (hipStream_t)stream, h, h_seg_stride, w1, b1, w2, b2, out, out_seg_stride, T, tiles);
-  }
-  SOPRO_LAUNCH_CHECK();
+  if (passes == 3) return launch_res<seanet_res128_kernel<3>, RES_LDS>(h, h_seg_stride, w1, b1, w2, b2, out, out_seg_stride, B, T, (hipStream_t)stream);
+  // the engine's bf16 mode: hi * hi only
+  return launch_res<seanet_res128_kernel<1>, RES_LDS>(h, h_seg_stride, w1, b1, w2, b2, out, out_seg_stride, B, T, (hipStream_t)stream);
 }
 
 // bf16 rows in (raw h), bf16 rows out (the activated result): the bf16 mode's activation flow, one pass.  Strides count bf16 elements.
@@ -466,13 +391,8 @@ extern "C" int sopro_seanet_res128_bf16(const void* h, int64_t h_seg_stride, con
   SOPRO_CHECK_ARG(aligned16(h) && aligned16(w1) && aligned16(w2) && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (h_seg_stride & 7) == 0 && (out_seg_stride & 1) == 0,
                   "alignment (h rows in 16-byte pieces, out in 4-byte pairs)");
   SOPRO_CHECK_ARG(h_seg_stride >= (int64_t)(T + 2) * RC && out_seg_stride >= (int64_t)(T + 2) * RC, "segments hold 2 + T rows of 128 bf16");
-  const int ntile = (T + RTO - 1) / RTO;
-  const int64_t all = (int64_t)ntile * B;
-  const int tiles = g_res_tiles > 0 ? g_res_tiles : (all >= 16 * 2048 ? 16 : (all >= 8 * 1024 ? 8 : (all >= 2048 ? 2 : 1)));
-  dim3 grid((ntile + tiles - 1) / tiles, B);
-  hipLaunchKernelGGL(seanet_res128_hb_kernel, grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const unsigned short*>(h), h_seg_stride, w1, b1, w2, b2,
-                     reinterpret_cast<unsigned short*>(out), out_seg_stride, T, tiles);
-  SOPRO_LAUNCH_CHECK();
+  return launch_res<seanet_res128_hb_kernel, 0>(reinterpret_cast<const unsigned short*>(h), h_seg_stride, w1, b1, w2, b2, reinterpret_cast<unsigned short*>(out),
+                                                out_seg_stride, B, T, (hipStream_t)stream);
 }
 
 extern "C" int sopro_seanet_res128_f32(const float* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2,

@@ -18,28 +18,16 @@
 // accumulator layout) and the last layer's weights are requested in the tile's memory round.  2 workgroups per CU (55 KB LDS).
 #include <type_traits>
 
-#include "common.h"
+#include "seanet_mma.h"
 
 namespace {
 
 constexpr int TO = 126;        // output samples per tile
 constexpr int HR = TO + 4;     // h rows in LDS (samples s0-4 .. s0+TO-1)
-constexpr int EROW = 272;      // bytes per row of the split h tile: 64 hi | 64 lo | pad
+constexpr int EROW = split_row_bytes(64);  // 272: row of the split h tile
 constexpr int YR = TO + 2;     // rows of the 32-channel intermediate (samples s0-2 .. s0+TO-1) == 128 == 4 MFMA row tiles
-constexpr int YROW = 144;      // bytes per row of the split intermediate: 32 hi | 32 lo | pad
+constexpr int YROW = split_row_bytes(32);  // 144: row of the split intermediate
 constexpr int HLD = 68;        // floats per row of the ELU(h') tile (written over the split h tile)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ bf16x8 frag(const uint4& v) { return *reinterpret_cast<const bf16x8*>(&v); }
-
-// 8 consecutive fp32 weights -> (hi, lo) fragments
-__device__ __forceinline__ void split8(const float* __restrict__ p, uint4& hi, uint4& lo) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  split2_bf16(a.x, a.y, hi.x, lo.x);
-  split2_bf16(a.z, a.w, hi.y, lo.y);
-  split2_bf16(b.x, b.y, hi.z, lo.z);
-  split2_bf16(b.z, b.w, hi.w, lo.w);
-}
 
 template <bool LOOP>
 __global__ __launch_bounds__(256, 2) void seanet_tail_kernel(const float* __restrict__ h, int64_t h_seg_stride,
@@ -142,17 +130,17 @@ __global__ __launch_bounds__(256, 2) void seanet_tail_kernel(const float* __rest
     // its 32 registers are free for the fragment reads that run ahead of the MFMAs - and consumed behind the next phase's
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mr = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg;
+      const int mr = wave * 32 + acc32_row(r) + 4 * fg;
       const int p = s0 + mr;  // padded row of sample s0-2+mr
       const bool in = p >= 2 && p < T + 2;
       const float* hp = hb + (int64_t)(in ? p : 0) * 64 + frow;  // outside: padded row 0, a zero row
       skip[0][r] = hp[0];
       skip[1][r] = hp[32];
     }
-    // D[r]: row (r&3) + 8*(r>>2) + 4*(lane>>5), column lane&31 -> ELU, split, one bf16 per plane
+    // accumulator layout (seanet_mma.h) -> ELU, split, one bf16 per plane
 #pragma unroll
     for (int r = 0; r < 16; r += 1) {
-      const int mr = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg;
+      const int mr = wave * 32 + acc32_row(r) + 4 * fg;
       unsigned hi, lo;
       split2_bf16(eluf_(acc[r] + b1v), 0.f, hi, lo);
       *reinterpret_cast<unsigned short*>(ys + mr * YROW + frow * 2) = (unsigned short)(hi & 0xffffu);
@@ -182,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void seanet_tail_kernel(const float* __rest
     float* hs = reinterpret_cast<float*>(es);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mr = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * fg;
+      const int mr = wave * 32 + acc32_row(r) + 4 * fg;
       const bool real = (s0 - 2 + mr) >= 0;  // samples before the utterance start are the zero padding of the last conv
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -231,12 +219,6 @@ constexpr int W2F = 4 * 2;         // second: [column tile][hi | lo]
 constexpr int TAIL3_LDS = (W1F + W2F) * 1024 + 16 * (ES3 + YS3);
 static_assert(16 * HLD * 4 <= ES3, "the fp32 ELU(h') tile must fit over the split h tile");
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void tail_wave_sync() {  // a wave's own LDS writes -> its other lanes' reads (see ar_driver.hip wave_lds_sync)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // HB (round 4: the bf16 mode's activation flow; PASSES == 1): h is bf16 rows (128 bytes per sample row: the 3.1 GB level is read at
 // half the bytes); the tile request is three 16-byte pieces per lane, ELU is applied to the widened values and the result is
@@ -337,7 +319,7 @@ __global__ __launch_bounds__(1024, 1) void seanet_tail16_kernel(const float* __r
         }
       }
     }
-    tail_wave_sync();
+    wave_lds_sync();
     // the staging registers are free: the next tile's rows travel while this one computes
     if (it + 1 < trips && s0 + 16 * T3O < T) request(s0 + 16 * T3O);
     // skip operand of the residual block in the accumulator layout of the second convolution (row 4 kq + i of the intermediate
@@ -392,7 +374,7 @@ __global__ __launch_bounds__(1024, 1) void seanet_tail16_kernel(const float* __r
           }
         }
     }
-    tail_wave_sync();  // (this wave is also done reading the split h tile: its memory becomes the ELU(h') tile below)
+    wave_lds_sync();  // (this wave is also done reading the split h tile: its memory becomes the ELU(h') tile below)
 
     // ---- conv k=1, 32 -> 64 on the intermediate, + skip operand, ELU(h') -> fp32 tile rows 0 .. 15 (row m = sample s0-2+m)
     {
@@ -422,7 +404,7 @@ __global__ __launch_bounds__(1024, 1) void seanet_tail16_kernel(const float* __r
         for (int nt = 0; nt < 4; ++nt) hs[m * HLD + 16 * nt + col] = real ? eluf_(skip[nt][i] + acc2[nt][i] + b2v[nt]) : 0.f;
       }
     }
-    tail_wave_sync();
+    wave_lds_sync();
 
     // ---- last conv k=3, 64 -> 1 on the stored ELU(h'): lane = channel; 16 column reads (the whole tile: 4 KB of LDS traffic
     // instead of 48 KB with one output per lane group), three FMAs per output, then a transpose-reduction over the 64 lanes:
@@ -454,13 +436,29 @@ __global__ __launch_bounds__(1024, 1) void seanet_tail16_kernel(const float* __r
       const int i = lane >> 2;
       if ((lane & 3) == 0 && i < T3O && s0 + i < T) wav[(int64_t)b * wav_seg_stride + s0 + i] = sum + bf;
     }
-    tail_wave_sync();  // the last phase is done with the LDS tiles before the next trip's staging
+    wave_lds_sync();  // the last phase is done with the LDS tiles before the next trip's staging
   }
+}
+
+int g_tail_tiles = 0;  // developer probe / tests: tiles per workgroup of the four-wave kernel, 0 = by size, < 0 = the sixteen-wave kernel
+
+// The sixteen-wave kernel: `trips` sixteen-tile rounds per workgroup (the fragments are made once per workgroup).  SHORT1: inputs
+// of fewer than 1024 wave tiles run one round (the kernel on bf16 rows, which takes every size).
+template <auto KERN, bool SHORT1>
+int launch_tail16(const float* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2, const float* b2, const float* wf, float bf,
+                  float* wav, int64_t wav_seg_stride, int32_t B, int32_t T, hipStream_t s) {
+  const int64_t all16 = (int64_t)((T + T3O - 1) / T3O) * B;
+  const int n16 = (int)(((T + T3O - 1) / T3O + 15) / 16);  // sixteen-tile rounds per utterance
+  int trips = all16 >= 64 * 4096 ? 32 : (all16 >= 16 * 4096 ? 8 : (SHORT1 && all16 < 1024 ? 1 : 2));
+  if (g_tail_tiles < -1) trips = -g_tail_tiles;  // (developer probe)
+  SOPRO_SET_MAX_LDS_ONCE(KERN, TAIL3_LDS);
+  hipLaunchKernelGGL(KERN, dim3((n16 + trips - 1) / trips, B), dim3(1024), TAIL3_LDS, s, h, h_seg_stride, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, T,
+                     trips);
+  SOPRO_LAUNCH_CHECK();
 }
 
 }  // namespace
 
-static int g_tail_tiles = 0;  // developer probe / tests: tiles per workgroup of the four-wave kernel, 0 = by size, < 0 = the sixteen-wave kernel
 extern "C" int sopro_seanet_tail_set_tiles(int tiles) {
   g_tail_tiles = tiles;
   return 0;
@@ -475,18 +473,10 @@ extern "C" int sopro_seanet_tail_p_f32(const float* h, int64_t h_seg_stride, con
   // long inputs: sixteen autonomous waves per CU over LDS-resident weight fragments (a wave owns whole tiles of 14 samples)
   const int64_t all16 = (int64_t)((T + T3O - 1) / T3O) * B;
   if (g_tail_tiles < 0 || (g_tail_tiles == 0 && all16 >= 16 * 1024)) {
-    const int n16 = (int)(((T + T3O - 1) / T3O + 15) / 16);  // sixteen-tile rounds per utterance
-    int trips = all16 >= 64 * 4096 ? 32 : (all16 >= 16 * 4096 ? 8 : 2);  // rounds per workgroup (the fragments are made once per workgroup)
-    if (g_tail_tiles < -1) trips = -g_tail_tiles;                         // (developer probe)
-    SOPRO_SET_MAX_LDS_ONCE(seanet_tail16_kernel<3>, TAIL3_LDS);
-    SOPRO_SET_MAX_LDS_ONCE(seanet_tail16_kernel<1>, TAIL3_LDS);
     if (passes == 3)
-      hipLaunchKernelGGL(seanet_tail16_kernel<3>, dim3((n16 + trips - 1) / trips, B), dim3(1024), TAIL3_LDS, (hipStream_t)stream, h, h_seg_stride, w1, b1,
-                         w2, b2, wf, bf, wav, wav_seg_stride, T, trips);
-    else  // the engine's bf16 mode: hi * hi only (short inputs below keep the three-pass four-wave kernel)
-      hipLaunchKernelGGL(seanet_tail16_kernel<1>, dim3((n16 + trips - 1) / trips, B), dim3(1024), TAIL3_LDS, (hipStream_t)stream, h, h_seg_stride, w1, b1,
-                         w2, b2, wf, bf, wav, wav_seg_stride, T, trips);
-    SOPRO_LAUNCH_CHECK();
+      return launch_tail16<seanet_tail16_kernel<3>, false>(h, h_seg_stride, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T, (hipStream_t)stream);
+    // the engine's bf16 mode: hi * hi only (short inputs below keep the three-pass four-wave kernel)
+    return launch_tail16<seanet_tail16_kernel<1>, false>(h, h_seg_stride, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T, (hipStream_t)stream);
   }
   const int ntile = (T + TO - 1) / TO;
   // several tiles per workgroup once there are enough of them to keep every CU supplied (>= 8 workgroups per CU after the grouping)
@@ -508,15 +498,8 @@ extern "C" int sopro_seanet_tail_bf16(const void* h, int64_t h_seg_stride, const
                                        int32_t T, void* stream) {
   SOPRO_CHECK_ARG(h && w1 && b1 && w2 && b2 && wf && wav && B > 0 && T > 0, "bad pointers or sizes");
   SOPRO_CHECK_ARG(aligned16(h) && aligned16(w1) && aligned16(w2) && aligned16(wf) && (h_seg_stride & 7) == 0, "alignment (h rows in 16-byte pieces)");
-  const int64_t all16 = (int64_t)((T + T3O - 1) / T3O) * B;
-  const int n16 = (int)(((T + T3O - 1) / T3O + 15) / 16);
-  int trips = all16 >= 64 * 4096 ? 32 : (all16 >= 16 * 4096 ? 8 : (all16 >= 1024 ? 2 : 1));
-  if (g_tail_tiles < -1) trips = -g_tail_tiles;
-  auto kern = seanet_tail16_kernel<1, true>;
-  SOPRO_SET_MAX_LDS_ONCE(kern, TAIL3_LDS);
-  hipLaunchKernelGGL(kern, dim3((n16 + trips - 1) / trips, B), dim3(1024), TAIL3_LDS, (hipStream_t)stream, reinterpret_cast<const float*>(h), h_seg_stride, w1, b1,
-                     w2, b2, wf, bf, wav, wav_seg_stride, T, trips);
-  SOPRO_LAUNCH_CHECK();
+  return launch_tail16<seanet_tail16_kernel<1, true>, true>(reinterpret_cast<const float*>(h), h_seg_stride, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T,
+                                                             (hipStream_t)stream);
 }
 
 extern "C" int sopro_seanet_tail_f32(const float* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2,

@@ -28,7 +28,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "seanet_mma.h"
 
 namespace {
 
@@ -36,11 +36,11 @@ constexpr int FC = 128;                 // input channels
 constexpr int FTI = 32;                 // input rows per tile
 constexpr int FTS = 4 * FTI;            // samples per tile
 constexpr int FXR = FTI + 1;            // staged x rows
-constexpr int FXROW = 2 * FC * 2 + 16;  // 528 B: [128 hi | 128 lo] bf16 + pad
-constexpr int FHROW = 272;              // h tile row: [64 hi | 64 lo] bf16 + pad; h' tile row: 64 fp32 + pad
+constexpr int FXROW = split_row_bytes(FC);  // 528 B: [128 hi | 128 lo] bf16 + pad
+constexpr int FHROW = split_row_bytes(64);  // 272 B, h tile row: [64 hi | 64 lo] bf16 + pad; h' tile row: 64 fp32 + pad
 constexpr int FHLD = FHROW / 4;         // 68 floats
 constexpr int FHR = FTS + 2;            // h / h' tile rows: two carried rows in front
-constexpr int FYROW = 144;              // y tile row: [32 hi | 32 lo] bf16 + pad
+constexpr int FYROW = split_row_bytes(32);  // 144 B, y tile row: [32 hi | 32 lo] bf16 + pad
 constexpr int FW1B = 2 * 6 * 2;         // first convolution: [column tile][k-step][hi | lo] blocks of 64 lanes x 16 B (16x16x32 B operands)
 constexpr int FW2B = 2 * 2 * 2;         // second: [channel half][substep][hi | lo] (32x32x16 B operands)
 constexpr int FCARRY = 2 * FHROW;       // 544 B: two rows
@@ -49,17 +49,7 @@ constexpr int FUSE_LDS = 2 * FXBUF + 2 * FHR * FHROW + FTS * FYROW + (FW1B + FW2
 static_assert(FUSE_LDS <= 160 * 1024, "LDS");
 static_assert(FXBUF % 16 == 0 && (FHR * FHROW) % 16 == 0 && (FTS * FYROW) % 16 == 0, "16-byte aligned LDS regions");
 
-typedef __bf16 fbf16x8 __attribute__((ext_vector_type(8)));
 typedef float ff32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ fbf16x8 ffrag(const uint4& v) { return *reinterpret_cast<const fbf16x8*>(&v); }
-
-__device__ __forceinline__ void fsplit8(const float* __restrict__ p, uint4& hi, uint4& lo) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  split2_bf16(a.x, a.y, hi.x, lo.x);
-  split2_bf16(a.z, a.w, hi.y, lo.y);
-  split2_bf16(b.x, b.y, hi.z, lo.z);
-  split2_bf16(b.z, b.w, hi.w, lo.w);
-}
 
 // Two lanes that hold neighbouring columns (channels c, c + 1) each hold a packed pair of bf16 - row A in the low half, row B in the
 // high half - of their column.  Afterwards the even lane holds row A of columns (c, c + 1) and the odd lane row B of the same two
@@ -162,7 +152,7 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
 #pragma unroll
   for (int s = 0; s < 16; ++s) {
     uint4 lo;
-    fsplit8(wu + (int64_t)(wave * 32 + frow) * (2 * FC) + s * 16 + fg * 8, wh[s], lo);
+    split8(wu + (int64_t)(wave * 32 + frow) * (2 * FC) + s * 16 + fg * 8, wh[s], lo);
     if (PASSES == 3) wl[s] = lo;
     if ((s & 3) == 3) asm volatile("" ::: "memory");  // four substeps per memory round
   }
@@ -171,14 +161,14 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
   for (int c = wave; c < 12; c += 8) {  // first convolution, 16x16x32 B operand: n = 16 nt + col, k = 32 s + 8 kq .. + 7 (k = tap * 64 + channel)
     const int nt = c / 6, s = c % 6;
     uint4 hi, lo;
-    fsplit8(w1 + (16 * nt + col) * 192 + s * 32 + kq * 8, hi, lo);
+    split8(w1 + (16 * nt + col) * 192 + s * 32 + kq * 8, hi, lo);
     w1s[((nt * 6 + s) * 2 + 0) * 64 + lane] = hi;
     w1s[((nt * 6 + s) * 2 + 1) * 64 + lane] = lo;
   }
   if (wave < 4) {  // second convolution, 32x32x16 B operand: n = 32 half + (lane & 31), k = 16 s + 8 (lane >> 5) .. + 7
     const int half = wave >> 1, s = wave & 1;
     uint4 hi, lo;
-    fsplit8(w2 + (half * 32 + frow) * 32 + s * 16 + fg * 8, hi, lo);
+    split8(w2 + (half * 32 + frow) * 32 + s * 16 + fg * 8, hi, lo);
     w2s[((half * 2 + s) * 2 + 0) * 64 + lane] = hi;
     w2s[((half * 2 + s) * 2 + 1) * 64 + lane] = lo;
   }
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
 #pragma unroll
       for (int s = 0; s < 6; ++s) {
         uint4 lo;
-        fsplit8(w1 + (16 * nt + col) * 192 + s * 32 + kq * 8, w1r[PASSES == 1 ? nt : 0][PASSES == 1 ? s : 0], lo);
+        split8(w1 + (16 * nt + col) * 192 + s * 32 + kq * 8, w1r[PASSES == 1 ? nt : 0][PASSES == 1 ? s : 0], lo);
       }
   }
   if (tid < 2 * FCARRY / 16) chs[tid] = make_uint4(0u, 0u, 0u, 0u);  // both carries: the zero padding at the head of an utterance
@@ -222,11 +212,11 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
       if constexpr (s + 1 < 16) p_read(xt, s + 1);
     }
     if constexpr (PASSES == 3) {
-      if constexpr (piece == 0) accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(pal), ffrag(wh[s]), accP, 0, 0, 0);
-      else if constexpr (piece == 1) accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(pah), ffrag(wl[s]), accP, 0, 0, 0);
-      else accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(pah), ffrag(wh[s]), accP, 0, 0, 0);
+      if constexpr (piece == 0) accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(pal), frag(wh[s]), accP, 0, 0, 0);
+      else if constexpr (piece == 1) accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(pah), frag(wl[s]), accP, 0, 0, 0);
+      else accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(pah), frag(wh[s]), accP, 0, 0, 0);
     } else {
-      accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(pah), ffrag(wh[s]), accP, 0, 0, 0);
+      accP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(pah), frag(wh[s]), accP, 0, 0, 0);
     }
   };
   // MFMAs [J0, J1) dealt evenly over NS slots of vector work: slot I issues its share, then the caller's instructions follow
@@ -238,7 +228,7 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
   constexpr int JA = 10 * PASSES, JB = 12 * PASSES;  // I3: [0, JA) of the tile after next; I1: [JA, JB); I2: [JB, NP)
 
   // ---- h(k+1): the finished accumulators, raw (+ bias) into registers for the skip operand; ELU + split into the h tile in
-  // NSH chunks (h_elu).  Register q of a lane is input row t = 8 (q / 4) + 4 (lane >> 5) + q % 4 = sample 4 t + phase, channel
+  // NSH chunks (h_elu).  Register q of a lane is input row t = acc32_row(q) + 4 (lane >> 5) (seanet_mma.h) = sample 4 t + phase, channel
   // cbase + (lane & 31); (q, q + 1) are tile rows j, j + 4 of this lane's channel: after pair_rows the even lane stores row j,
   // the odd lane row j + 4, channels (c, c + 1) each.
   auto h_raw = [&]() {
@@ -251,7 +241,7 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
   unsigned char* const hp0 = hs + (2 + ph + (odd ? 4 : 0)) * FHROW + (cbase + (frow & ~1)) * 2;
   auto h_elu = [&](auto i_) {  // chunk I of 8: registers 2 I, 2 I + 1
     constexpr int q = 2 * decltype(i_)::value;
-    const int t = 8 * (q >> 2) + 4 * fg + (q & 3);
+    const int t = acc32_row(q) + 4 * fg;
     unsigned hi, lo;
     split2_bf16(eluf_(hraw[q]), eluf_(hraw[q + 1]), hi, lo);
     unsigned char* hq = hp0 + 4 * t * FHROW;
@@ -276,16 +266,16 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
           const uint4 bh1 = w1s[((1 * 6 + s) * 2 + 0) * 64 + lane], bl1 = w1s[((1 * 6 + s) * 2 + 1) * 64 + lane];
           p_slot(xt, IC<JA>(), IC<JB>(), s_, IC<10>());  // (under the fragment reads' latency)
           // the two column tiles' chains alternate: a dependent MFMA waits for its predecessor's result
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(al), ffrag(bh0), acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(al), ffrag(bh1), acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(ah), ffrag(bl0), acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(ah), ffrag(bl1), acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(ah), ffrag(bh0), acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(ah), ffrag(bh1), acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh0), acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh1), acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl0), acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl1), acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh0), acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh1), acc[1], 0, 0, 0);
         } else {
           p_slot(xt, IC<JA>(), IC<JB>(), s_, IC<10>());
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(ah), ffrag(w1r[0][PASSES == 1 ? s : 0]), acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ffrag(ah), ffrag(w1r[PASSES == 1 ? 1 : 0][PASSES == 1 ? s : 0]), acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(w1r[0][PASSES == 1 ? s : 0]), acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(w1r[PASSES == 1 ? 1 : 0][PASSES == 1 ? s : 0]), acc[1], 0, 0, 0);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -332,11 +322,11 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
       p_slot(xt, IC<JB>(), IC<NP>(), m_, IC<NC2 + 8>());
       {
         if constexpr (PASSES == 3) {
-          if constexpr (piece == 0) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(al[s]), ffrag(bh[s]), acc2, 0, 0, 0);
-          else if constexpr (piece == 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(ah[s]), ffrag(bl[s]), acc2, 0, 0, 0);
-          else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(ah[s]), ffrag(bh[s]), acc2, 0, 0, 0);
+          if constexpr (piece == 0) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(al[s]), frag(bh[s]), acc2, 0, 0, 0);
+          else if constexpr (piece == 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(ah[s]), frag(bl[s]), acc2, 0, 0, 0);
+          else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(ah[s]), frag(bh[s]), acc2, 0, 0, 0);
         } else {
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag(ah[s]), ffrag(bh[s]), acc2, 0, 0, 0);
+          acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(ah[s]), frag(bh[s]), acc2, 0, 0, 0);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -348,7 +338,7 @@ __global__ __launch_bounds__(512, 1) void seanet_uptail_kernel(const void* __res
       {
 #pragma unroll
         for (int q = q0; q < q0 + 2; ++q) {
-          const int t = 8 * (q >> 2) + 4 * fg + (q & 3);
+          const int t = acc32_row(q) + 4 * fg;
           hf[(2 + 4 * t + ph) * FHLD + cbase + frow] = eluf_(hraw[q] + acc2[q] + b2v);
         }
       }

@@ -315,8 +315,7 @@ def test_seanet_tail_on_bf16_rows(B, T):
     close(wav, full, 3e-2 * float(full.abs().max() + 1.0), "tail on bf16 rows vs fp32 layers")
 
 
-def test_seanet_res128_on_bf16_rows():
-    B, T = 3, 333
+def _seanet_res128_bf16_case(B, T, tiles_list):
     h = rnd(B, T, 128, seed=720)
     w1, b1 = rnd(64, 128, 3, seed=721, scale=0.05), rnd(64, seed=722, scale=0.1)
     w2, b2 = rnd(128, 64, 1, seed=723, scale=0.12), rnd(128, seed=724, scale=0.1)
@@ -326,10 +325,11 @@ def test_seanet_res128_on_bf16_rows():
     y = O.causal_conv1d(bf(F.elu(x)), bf(w1), b1)
     y = O.causal_conv1d(bf(F.elu(y)), bf(w2), b2)
     ref = F.elu(x + y).transpose(1, 2)
+    assert ref.shape == (B, T, 128) and bool(torch.isfinite(ref).all())
     args = [dev(hb)] + [dev(t) for t in (pack.pack_conv1d(w1), b1, pack.pack_conv1d(w2), b2)]
     lib, outs = hip.load(), []
     try:
-        for tiles in (0, 1, 4):
+        for tiles in tiles_list:
             lib.sopro_seanet_res_set_tiles(tiles)
             out = torch.full((B, 2 + T + 5, 128), float("nan"), dtype=torch.bfloat16, device=DEV)
             out[:, :2] = 0.0
@@ -346,10 +346,18 @@ def test_seanet_res128_on_bf16_rows():
         assert torch.equal(o[:, 2:2 + T], outs[0][:, 2:2 + T])
 
 
-def test_seanet_up128_on_bf16_rows_equals_the_tile_kernel():
-    """The weight-stationary transposed convolution on bf16 rows: bit for bit what sopro_gemm_bf16x1 (a_format 2, c_mode 6) gives
-    on the same operands, for any number of tiles per workgroup; and torch's conv_transpose1d on the rounded operands."""
-    B, T, ci, co, r = 3, 333, 128, 64, 4
+def test_seanet_res128_on_bf16_rows():
+    _seanet_res128_bf16_case(3, 333, (0, 1, 4))
+
+
+@pytest.mark.parametrize("T", [1, 64, 65])
+def test_seanet_res128_on_bf16_rows_at_the_tile_edges(T):
+    """Where the 64-row tile walk can go wrong: one row, one whole tile, a whole tile with a one-row tile behind it."""
+    _seanet_res128_bf16_case(2, T, (0, 1, 2))
+
+
+def _seanet_up128_bf16_case(B, T, tiles_list):
+    ci, co, r = 128, 64, 4
     x = rnd(B, T, ci, seed=760)
     wt, bt = rnd(ci, co, 2 * r, seed=761, scale=0.06), rnd(co, seed=762, scale=0.1)
     W, bias = pack.pack_convtr1d(wt, bt, r)
@@ -357,10 +365,11 @@ def test_seanet_up128_on_bf16_rows_equals_the_tile_kernel():
     xb = torch.zeros(B, 1 + T + 7, ci, dtype=torch.bfloat16)
     xb[:, 1:1 + T] = b16(x)
     ref = F.conv_transpose1d(xb[:, 1:1 + T].float().transpose(1, 2), bf(wt), bt, stride=r)[..., :T * r].transpose(1, 2)
+    assert ref.shape == (B, T * r, co) and bool(torch.isfinite(ref).all())
     xd, Wd, bd = dev(xb), dev(W), dev(bias)
     lib, outs = hip.load(), []
     try:
-        for tiles in (0, 1, 2, 5):
+        for tiles in tiles_list:
             lib.sopro_seanet_up_set_tiles(tiles)
             out = torch.full((B, 2 + T * r + 6, co), float("nan"), dtype=torch.bfloat16, device=DEV)
             hip.seanet_up128_bf16(xd, Wd, bd, out, B=B, T=T, x_seg_stride=xs, out_seg_stride=os_, out_off=2 * co)
@@ -378,6 +387,18 @@ def test_seanet_up128_on_bf16_rows_equals_the_tile_kernel():
              ldc=r * co, c_mode=6)
     torch.cuda.synchronize()
     assert torch.equal(out2.cpu()[:, 2:2 + T * r], got)
+
+
+def test_seanet_up128_on_bf16_rows_equals_the_tile_kernel():
+    """The weight-stationary transposed convolution on bf16 rows: bit for bit what sopro_gemm_bf16x1 (a_format 2, c_mode 6) gives
+    on the same operands, for any number of tiles per workgroup; and torch's conv_transpose1d on the rounded operands."""
+    _seanet_up128_bf16_case(3, 333, (0, 1, 2, 5))
+
+
+@pytest.mark.parametrize("T", [1, 64, 65])
+def test_seanet_up128_on_bf16_rows_at_the_tile_edges(T):
+    """Where the 64-row tile walk can go wrong: one row, one whole tile, a whole tile with a one-row tile behind it."""
+    _seanet_up128_bf16_case(2, T, (0, 1, 2))
 
 
 def test_mimi_decode_bf16_rows_against_the_fp32_rows_form(cfg, mimi_np, mc):

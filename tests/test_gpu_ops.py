@@ -1276,10 +1276,7 @@ def test_seanet_tail_sixteen_wave_kernel(B, T):
     assert float((outs[-1] - outs[1]).abs().max()) < 2e-6 * float(ref.abs().max() + 1.0)
 
 
-def test_seanet_res128_fused_block_matches_the_layers():
-    """MimiResnetBlock(dim 128) + the next layer's ELU in one weight-stationary kernel (HF:modeling_mimi.py:408-447):
-    against torch's convolutions, for one and several tiles per workgroup (bit-identical), partial last tile, batch of 3."""
-    B, T = 3, 333  # 6 tiles of 64 rows, the last one partial
+def _seanet_res128_case(B, T, tiles_list):
     h = rnd(B, T, 128, seed=720)
     w1, b1 = rnd(64, 128, 3, seed=721, scale=0.05), rnd(64, seed=722, scale=0.1)
     w2, b2 = rnd(128, 64, 1, seed=723, scale=0.12), rnd(128, seed=724, scale=0.1)
@@ -1287,12 +1284,13 @@ def test_seanet_res128_fused_block_matches_the_layers():
     y = O.causal_conv1d(F.elu(x), w1, b1)
     y = O.causal_conv1d(F.elu(y), w2, b2)
     ref = F.elu(x + y).transpose(1, 2)
+    assert ref.shape == (B, T, 128) and bool(torch.isfinite(ref).all())
     hb = torch.zeros(B, 2 + T + 5, 128)  # segment stride larger than the rows in use
     hb[:, 2:2 + T] = h
     args = [dev(t) for t in (hb, pack.pack_conv1d(w1), b1, pack.pack_conv1d(w2), b2)]
     lib, outs = hip.load(), []
     try:
-        for tiles in (0, 1, 2, 4):
+        for tiles in tiles_list:
             lib.sopro_seanet_res_set_tiles(tiles)
             out = torch.full((B, 2 + T + 5, 128), float("nan"), device=DEV)
             out[:, :2] = 0.0
@@ -1305,8 +1303,22 @@ def test_seanet_res128_fused_block_matches_the_layers():
     assert bool(torch.isnan(outs[0][:, 2 + T:]).all()) and float(outs[0][:, :2].abs().max()) == 0.0  # nothing outside rows 2 .. 2+T
     for o in outs[1:]:
         assert torch.equal(o[:, 2:2 + T], outs[0][:, 2:2 + T])
+    return args
+
+
+def test_seanet_res128_fused_block_matches_the_layers():
+    """MimiResnetBlock(dim 128) + the next layer's ELU in one weight-stationary kernel (HF:modeling_mimi.py:408-447):
+    against torch's convolutions, for one and several tiles per workgroup (bit-identical), partial last tile, batch of 3."""
+    B, T = 3, 333  # 6 tiles of 64 rows, the last one partial
+    args = _seanet_res128_case(B, T, (0, 1, 2, 4))
     with pytest.raises(hip.SoproHipError):
         hip.seanet_res128(args[0], *args[1:], args[0], B=B, T=T, h_seg_stride=(2 + T + 5) * 128, out_seg_stride=(2 + T + 5) * 128)
+
+
+@pytest.mark.parametrize("T", [1, 64, 65])
+def test_seanet_res128_fused_block_at_the_tile_edges(T):
+    """The same checks where the 64-row tile walk can go wrong: one row, one whole tile, a whole tile with a one-row tile behind it."""
+    _seanet_res128_case(2, T, (0, 1, 2))
 
 
 def test_host_mirror_copies_behind_the_queued_launches():
@@ -1334,16 +1346,12 @@ def test_host_mirror_copies_behind_the_queued_launches():
     assert back.tolist() == [5, 4, 3, 2, 1, 0]
 
 
-@pytest.mark.parametrize("passes", [3, 1])
-def test_seanet_up128_weight_stationary_equals_the_tile_kernel(passes):
-    """Last transposed convolution of SEANet (ConvTranspose1d 128 -> 64, k = 8, s = 4; HF:modeling_mimi.py:931-961) in its
-    weight-stationary form: against torch's conv_transpose1d, bit for bit against the generic split-bf16 tile kernel on the
-    same operands (three-pass and bf16-mode one-pass), for any number of tiles per workgroup, partial last tile, batch of 3,
-    segment strides larger than the rows in use."""
-    B, T, ci, co, r = 3, 333, 128, 64, 4
+def _seanet_up128_case(B, T, passes, tiles_list):
+    ci, co, r = 128, 64, 4
     x = rnd(B, T, ci, seed=760)
     wt, bt = rnd(ci, co, 2 * r, seed=761, scale=0.06), rnd(co, seed=762, scale=0.1)
     ref = F.conv_transpose1d(x.transpose(1, 2), wt, bt, stride=r)[..., :T * r].transpose(1, 2)  # causal: trim the right tail
+    assert ref.shape == (B, T * r, co) and bool(torch.isfinite(ref).all())
     W, bias = pack.pack_convtr1d(wt, bt, r)  # [r*co, 2*ci], [r*co]
     xs, os_ = (1 + T + 3) * ci, (2 + T * r + 7) * co
     xb = torch.zeros(B, 1 + T + 3, ci)
@@ -1351,7 +1359,7 @@ def test_seanet_up128_weight_stationary_equals_the_tile_kernel(passes):
     xd, Wd, bd = dev(xb), dev(W), dev(bias)
     lib, outs = hip.load(), []
     try:
-        for tiles in (0, 1, 2, 5):
+        for tiles in tiles_list:
             lib.sopro_seanet_up_set_tiles(tiles)
             out = torch.full((B, 2 + T * r + 7, co), float("nan"), device=DEV)
             hip.seanet_up128(xd, Wd, bd, out, B=B, T=T, x_seg_stride=xs, out_seg_stride=os_, out_off=2 * co, passes=passes)
@@ -1371,8 +1379,26 @@ def test_seanet_up128_weight_stationary_equals_the_tile_kernel(passes):
              ldc=r * co)
     torch.cuda.synchronize()
     assert torch.equal(out2.cpu()[:, 2:2 + T * r], got)
+    return xd, Wd, bd, out2, xs, os_
+
+
+@pytest.mark.parametrize("passes", [3, 1])
+def test_seanet_up128_weight_stationary_equals_the_tile_kernel(passes):
+    """Last transposed convolution of SEANet (ConvTranspose1d 128 -> 64, k = 8, s = 4; HF:modeling_mimi.py:931-961) in its
+    weight-stationary form: against torch's conv_transpose1d, bit for bit against the generic split-bf16 tile kernel on the
+    same operands (three-pass and bf16-mode one-pass), for any number of tiles per workgroup, partial last tile, batch of 3,
+    segment strides larger than the rows in use."""
+    B, T = 3, 333
+    xd, Wd, bd, out2, xs, os_ = _seanet_up128_case(B, T, passes, (0, 1, 2, 5))
     with pytest.raises(hip.SoproHipError):
         hip.seanet_up128(xd, Wd, bd, out2, B=B, T=T, x_seg_stride=xs, out_seg_stride=os_, passes=2)
+
+
+@pytest.mark.parametrize("T", [1, 64, 65])
+@pytest.mark.parametrize("passes", [3, 1])
+def test_seanet_up128_weight_stationary_at_the_tile_edges(passes, T):
+    """The same checks where the 64-row tile walk can go wrong: one row, one whole tile, a whole tile with a one-row tile behind it."""
+    _seanet_up128_case(2, T, passes, (0, 1, 2))
 
 
 @pytest.mark.parametrize("N,K,glu", [(1536, 384, False), (384, 1536, False), (2049, 384, False), (768, 384, True)])

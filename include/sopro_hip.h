@@ -240,11 +240,15 @@ int sopro_gemm_auto_ksplit(int32_t M, int32_t N, int32_t K, int32_t pieces, int3
  * src/sopro/nn/blocks.py:26-37 whose weight vector the host has folded into W (W[n,k] * w_norm[k]); else rs = 1.
  * ksplit = 1 with K > 384: the K/384 slices go to different workgroups and Y receives K/384 partial results
  *   [slice][B][ldy] (y_part_stride elements apart); with EPI_RES slice 0 carries bias + residual, the other
- *   slices are raw; the consumer passes slice 0 as X and slices 1..3 as Xp.
+ *   slices are raw; the consumer passes slice 0 as X and slices 1..3 as Xp.  ksplit = 0 walks the slices in one workgroup.
+ *   A K-split call takes no `scale`: only slice 0 would be scaled, so the slices would not sum to R + scale * y (refused).
+ *   A K-split call with EPI_NONE takes no `bias` (and its aux set, where that one's epilogue is NONE, no `aux_bias`): without
+ *   a residual no slice carries the bias (refused).  K-split output takes EPI_NONE or EPI_RES only.
  *   EPI_GLU_DW (N == 2*K == 768, W in the natural torch layout [value rows | gate rows], rms_norm set):
  *     h = value*sigmoid(gate); ring[(t % L)][b] = h; y = dwconv taps over the ring; Y = Xin + y
  *     == SSMLiteBlock.forward_step first half, src/sopro/nn/blocks.py:150-157 and :76-110.
- *     `step` is a device pointer to the current frame index t; ksize <= 13. */
+ *     `step` is a device pointer to the current frame index t; ksize <= 13; ring_len == (ksize - 1) * dil + 1 (ksize 1: one
+ *     slot, dil is ignored). */
 typedef struct sopro_skinny_args {
   const float* X; int64_t ldx;
   const float* W; int64_t ldw;
@@ -269,7 +273,8 @@ typedef struct sopro_skinny_args {
   /* AUX column tiles (round 4, plain form only; all zero = none): `aux_tiles` (even) more 16-column tiles behind the main ones run the
    * same input rows against a second operand set (weights in the layout of w_layout, [16 * aux_tiles, K]) and write to aux_Y - the
    * query projection of the following text cross-attention block rides on the feed-forward launches (see sopro_ar_frame.k_unfold).
-   * aux_flags: bit 0 = no RMSNorm row scale, bit 1 = epilogue NONE (else the launch's epilogue with aux_bias / aux_R). */
+   * aux_flags: bit 0 = no RMSNorm row scale, bit 1 = epilogue NONE (else the launch's epilogue with aux_bias / aux_R).
+   * A launch with aux tiles takes no `scale` (it has N entries and the aux columns none of their own: refused). */
   const float* aux_W; const float* aux_bias; const float* aux_R; float* aux_Y;
   int64_t aux_ldy, aux_ldr, aux_y_part_stride;
   int32_t aux_tiles, aux_flags;

@@ -429,7 +429,7 @@ extern "C" int sopro_pack_skinny_w_bf16(const float* W, int64_t ldw, int32_t N, 
 
 extern "C" int sopro_skinny_f32(const sopro_skinny_args* p, void* stream) {
   SOPRO_CHECK_ARG(p != nullptr, "args is NULL");
-  const sopro_skinny_args& a = *p;
+  sopro_skinny_args a = *p;
   SOPRO_CHECK_ARG(a.B > 0 && a.N > 0 && a.K > 0, "B, N, K must be positive");
   SOPRO_CHECK_ARG((a.K % KS) == 0, "K must be a multiple of 384");
   SOPRO_CHECK_ARG(a.X && a.W && a.Y, "X, W, Y must be non-NULL");
@@ -448,13 +448,23 @@ extern "C" int sopro_skinny_f32(const sopro_skinny_args* p, void* stream) {
     SOPRO_CHECK_ARG(a.ksize >= 1 && a.ksize <= MAXTAPS && a.dil >= 1 && a.ring_len == (a.ksize - 1) * a.dil + 1, "ring_len must be (ksize-1)*dil+1, ksize <= 13");
     SOPRO_CHECK_ARG(a.ring_bcap >= a.B && a.rms_norm, "ring_bcap < B, or rms_norm not set (the GLU tail always follows an RMSNorm)");
     SOPRO_CHECK_ARG(a.ring_format == 0 || (a.ring_format == 1 && a.w_layout == 2), "ring_format: 0 (fp32), or 1 (bf16 ring) with the bf16 weights of w_layout 2");
+    // ksize 1: the ring is one slot and no older tap is live.  The kernel still reads its twelve dead taps and wraps their slot
+    // by ONE subtraction of ring_len, which holds only for dil < ring_len: with dil > 1 the reads would leave the ring.
+    if (a.ksize == 1) a.dil = 1;
   }
   const int nslices = a.K / KS;
   const int gy = (a.ksplit && nslices > 1) ? nslices : 1;
   SOPRO_CHECK_ARG(gy == 1 || a.epilogue == SOPRO_EPI_NONE || a.epilogue == SOPRO_EPI_RES,
                   "K-split output takes EPI_NONE or EPI_RES (slice 0 then carries bias + residual; the consumer sums the slices)");
+  // What the kernel does not compute as the header's formula summed over the slices: only slice 0 would be scaled, and without a
+  // residual no slice carries the bias.
+  SOPRO_CHECK_ARG(gy == 1 || !a.scale, "K-split output takes no scale (only slice 0 would be scaled: the consumer's sum is not R + scale * y)");
+  SOPRO_CHECK_ARG(gy == 1 || a.epilogue != SOPRO_EPI_NONE || !a.bias, "K-split output with EPI_NONE takes no bias (no slice carries it)");
   SOPRO_CHECK_ARG(a.mt >= 0 && a.mt <= 2 && a.nt >= 0 && a.nt <= 2, "mt / nt must be 0 (= 1), 1 or 2");
   if (a.aux_tiles != 0) {
+    const int aux_epi = (a.aux_flags & 2) ? (int)SOPRO_EPI_NONE : a.epilogue;
+    SOPRO_CHECK_ARG(gy == 1 || aux_epi != SOPRO_EPI_NONE || !a.aux_bias, "K-split output: aux tiles with epilogue NONE take no aux_bias (no slice carries it)");
+    SOPRO_CHECK_ARG(!a.scale, "aux tiles take no scale (scale has N entries; the aux columns have none of their own)");
     SOPRO_CHECK_ARG(a.aux_tiles > 0 && (a.aux_tiles & 1) == 0 && !dw && a.w_layout != 0 && (a.N & 31) == 0,
                     "aux tiles: an even count, plain form, fragment-ordered weights, N a multiple of 32 (whole main tiles)");
     SOPRO_CHECK_ARG(a.aux_W && a.aux_Y && aligned16(a.aux_W) && ((a.aux_flags & 2) || a.epilogue != SOPRO_EPI_RES || a.aux_R), "aux tiles: aux_W, aux_Y (and aux_R for EPI_RES)");

@@ -455,7 +455,11 @@ int sopro_final_conv_f32(const float* h, int64_t h_seg_stride, const float* w, f
 
 /* Fused 24 kHz tail of the SEANet decoder: last MimiResnetBlock (dim 64: k=3 conv 64->32, k=1 conv 32->64, residual)
  * + last layer (ELU, k=3 conv 64->1), HF:modeling_mimi.py:408-447, 957-960.  h [B][2+T][64] (two zero rows in front of
- * each segment) is read once; only wav [B][T] is written.  w1 [32][3*64] (tap-major K), w2 [64][32], wf [3][64]. */
+ * each segment) is read once; only wav [B][T] is written.  w1 [32][3*64] (tap-major K), w2 [64][32], wf [3][64].
+ * Refused (all three tail entry points; -2, nothing written): h, w1, w2, wf not 16-byte aligned; h_seg_stride % 4 != 0 (% 8 on bf16
+ * rows); with B > 1, h_seg_stride < (2 + T) * 64 or wav_seg_stride < T (two workgroups would write the same words);
+ * T > 2^31 - 1025 (the kernels' 32-bit tile sample index: a walk ends at the first tile at or past T, so it stays below T + 448
+ * for every tiles / trips setting, the probes' included). */
 int sopro_seanet_tail_f32(const float* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2,
                           const float* b2, const float* wf, float bf, float* wav, int64_t wav_seg_stride, int32_t B,
                           int32_t T, void* stream);
@@ -467,7 +471,9 @@ int sopro_seanet_tail_p_f32(const float* h, int64_t h_seg_stride, const float* w
 /* Fused MimiResnetBlock at the 128-channel level of the SEANet decoder (HF:modeling_mimi.py:408-447, dim 128: k=3 conv
  * 128->64, k=1 conv 64->128, residual) followed by the ELU of the next layer: out = ELU(h + c2(ELU(c1(ELU(h))))).
  * h, out: [B][2 + T][128] (two zero rows in front of each segment; out's are not written), h != out.  w1 [64][3*128]
- * (tap-major K), w2 [128][64].  h is read once, out written once; both weight matrices stay in registers. */
+ * (tap-major K), w2 [128][64].  h is read once, out written once; both weight matrices stay in registers.
+ * Refused (-2, nothing written): passes other than 1 or 3; h == out; h, w1, w2, out not 16-byte aligned or a segment stride
+ * % 4 != 0; a segment stride < (2 + T) * 128 (for any B); T >= 2^21 (32-bit byte offsets (row * 128 + column) * 4, row <= T + 1). */
 int sopro_seanet_res128_f32(const float* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2, const float* b2,
                             float* out, int64_t out_seg_stride, int32_t B, int32_t T, void* stream);
 int sopro_seanet_res128_p_f32(const float* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2, const float* b2,
@@ -478,7 +484,10 @@ int sopro_seanet_res_set_tiles(int tiles); /* developer probe / tests: 64-row ti
  * whose row 0 of every segment is the zero row in front of the first sample, W [256][256] = pack_convtr1d's matrix (row =
  * output phase * 64 + channel, column = tap half * 128 + input channel), bias [256], out rows of 256 floats (= 4 output
  * samples x 64 channels).  Same results as sopro_gemm_bf16x3 (passes = 3) / sopro_gemm_bf16x1 (passes = 1) on that shape, bit
- * for bit; the weights are split once per workgroup and stay in registers. */
+ * for bit; the weights are split once per workgroup and stay in registers.
+ * Refused (-2, nothing written): passes other than 1 or 3; x, w, out not 16-byte aligned or a segment stride % 4 != 0; with B > 1,
+ * x_seg_stride < (T + 1) * 128 or out_seg_stride < T * 256; T > 2^31 - 129 (the 32-bit tile row index runs up to T + 127;
+ * both row types). */
 int sopro_seanet_up128_f32(const float* x, int64_t x_seg_stride, const float* w, const float* bias, float* out,
                            int64_t out_seg_stride, int32_t B, int32_t T, int32_t passes, void* stream);
 /* The bf16 mode's activation flow (round 4): the three fused SEANet kernels on bf16 ROWS in memory - half the bytes of the decoder's
@@ -486,7 +495,10 @@ int sopro_seanet_up128_f32(const float* x, int64_t x_seg_stride, const float* w,
  * to bf16 elements and the segment strides count bf16 elements; layouts as in the fp32 forms above.
  *   sopro_seanet_res128_bf16: h raw [B][2 + T][128] -> out = ELU(h + c2(ELU(c1(ELU(h))))) [B][2 + T][128]
  *   sopro_seanet_up128_bf16 : x activated [B][>= 1 + T][128] -> out rows of 256 (4 samples x 64 channels), raw
- *   sopro_seanet_tail_bf16  : h raw [B][2 + T][64] -> wav fp32 [B][T]  (the sixteen-wave kernel at any size) */
+ *   sopro_seanet_tail_bf16  : h raw [B][2 + T][64] -> wav fp32 [B][T]  (the sixteen-wave kernel at any size)
+ * Refusals as for the fp32 forms, with these differences: input rows come in 16-byte pieces (input segment stride % 8 == 0), bf16
+ * outputs go out in 4-byte pairs (out 4-byte aligned, out_seg_stride % 2 == 0); sopro_seanet_res128_bf16 takes T < 2^22 (32-bit
+ * byte offsets (row * 128 + column) * 2, row <= T + 1). */
 int sopro_seanet_res128_bf16(const void* h, int64_t h_seg_stride, const float* w1, const float* b1, const float* w2, const float* b2,
                              void* out, int64_t out_seg_stride, int32_t B, int32_t T, void* stream);
 int sopro_seanet_up128_bf16(const void* x, int64_t x_seg_stride, const float* w, const float* bias, void* out, int64_t out_seg_stride,
@@ -501,7 +513,10 @@ int sopro_seanet_up_set_tiles(int tiles); /* developer probe / tests: 64-row til
  * two kernels it replaces, wav [B][4 T] fp32.  passes 3 = three-pass split-bf16 (the decoder's class), 1 = one pass (bf16 mode).
  * Same operand rounding and accumulation per contraction as the two kernels; the sums of the last layer are taken in the order of
  * the sixteen-wave tail.  Written for long inputs (a workgroup walks >= 24 tiles of 32 input rows): the engine uses it from
- * 512 Ki input rows per call, the two kernels below that. */
+ * 512 Ki input rows per call, the two kernels below that.
+ * Refused (-2, nothing written): passes other than 1 or 3; x, wu, w1, w2 not 16-byte aligned; x_seg_stride % 4 != 0 (% 8 on bf16
+ * rows); with B > 1, x_seg_stride < (T + 1) * 128 or wav_seg_stride < 4 T; T > 2^29 - 65 (the 32-bit sample index runs up to
+ * 4 T + 255). */
 int sopro_seanet_uptail_f32(const float* x, int64_t x_seg_stride, const float* wu, const float* bu, const float* w1, const float* b1,
                             const float* w2, const float* b2, const float* wf, float bf, float* wav, int64_t wav_seg_stride, int32_t B,
                             int32_t T, int32_t passes, void* stream);

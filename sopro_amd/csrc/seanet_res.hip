@@ -391,6 +391,8 @@ extern "C" int sopro_seanet_res128_bf16(const void* h, int64_t h_seg_stride, con
   SOPRO_CHECK_ARG(aligned16(h) && aligned16(w1) && aligned16(w2) && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (h_seg_stride & 7) == 0 && (out_seg_stride & 1) == 0,
                   "alignment (h rows in 16-byte pieces, out in 4-byte pairs)");
   SOPRO_CHECK_ARG(h_seg_stride >= (int64_t)(T + 2) * RC && out_seg_stride >= (int64_t)(T + 2) * RC, "segments hold 2 + T rows of 128 bf16");
+  // lane_off / row_off / last_off of seanet_res128_hb_kernel: ((row) * RC + column) * 2 in 32-bit ints, row <= T + 1 -> (T + 2) * 256 < 2^31
+  SOPRO_CHECK_ARG(T < (1 << 22), "T must stay below 2^22 rows per utterance (32-bit byte offsets of the skip operand and the stores)");
   return launch_res<seanet_res128_hb_kernel, 0>(reinterpret_cast<const unsigned short*>(h), h_seg_stride, w1, b1, w2, b2, reinterpret_cast<unsigned short*>(out),
                                                 out_seg_stride, B, T, (hipStream_t)stream);
 }

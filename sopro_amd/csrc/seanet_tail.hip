@@ -457,6 +457,17 @@ int launch_tail16(const float* h, int64_t h_seg_stride, const float* w1, const f
   SOPRO_LAUNCH_CHECK();
 }
 
+// What every tail entry point checks about its strides and T: nullptr, or why the call is refused.
+// T: s0 = (tile0 + it * 16) * T3O of seanet_tail16_kernel and s0 = (blockIdx.x * tiles + it) * TO of seanet_tail_kernel are 32-bit
+// ints.  A workgroup's first tile starts below T + 16 * T3O (T + TO), and the walk ends at the first s0 >= T, so s0 stays below
+// T + 2 * 16 * T3O = T + 448 whatever tiles / trips are (the probes included); s0 + 16 * T3O and p < T + 2 ride on it.  Addresses are 64-bit.
+const char* tail_refusal(int64_t h_seg_stride, int64_t wav_seg_stride, int32_t B, int32_t T) {
+  if (B > 1 && (h_seg_stride < (int64_t)(T + 2) * 64 || wav_seg_stride < (int64_t)T))
+    return "segment strides: h holds 2 + T rows of 64 per utterance (two zero rows in front), wav T samples";
+  if (T > INT32_MAX - 1024) return "T must stay at or below 2^31 - 1025 samples per utterance (32-bit tile sample index)";
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" int sopro_seanet_tail_set_tiles(int tiles) {
@@ -470,6 +481,7 @@ extern "C" int sopro_seanet_tail_p_f32(const float* h, int64_t h_seg_stride, con
   SOPRO_CHECK_ARG(passes == 1 || passes == 3, "passes must be 3 (three-pass split-bf16) or 1 (bf16 mode)");
   SOPRO_CHECK_ARG(h && w1 && b1 && w2 && b2 && wf && wav && B > 0 && T > 0, "bad pointers or sizes");
   SOPRO_CHECK_ARG(aligned16(h) && aligned16(w1) && aligned16(w2) && aligned16(wf) && (h_seg_stride & 3) == 0, "alignment");
+  { const char* why = tail_refusal(h_seg_stride, wav_seg_stride, B, T); SOPRO_CHECK_ARG(!why, why); }
   // long inputs: sixteen autonomous waves per CU over LDS-resident weight fragments (a wave owns whole tiles of 14 samples)
   const int64_t all16 = (int64_t)((T + T3O - 1) / T3O) * B;
   if (g_tail_tiles < 0 || (g_tail_tiles == 0 && all16 >= 16 * 1024)) {
@@ -498,6 +510,7 @@ extern "C" int sopro_seanet_tail_bf16(const void* h, int64_t h_seg_stride, const
                                        int32_t T, void* stream) {
   SOPRO_CHECK_ARG(h && w1 && b1 && w2 && b2 && wf && wav && B > 0 && T > 0, "bad pointers or sizes");
   SOPRO_CHECK_ARG(aligned16(h) && aligned16(w1) && aligned16(w2) && aligned16(wf) && (h_seg_stride & 7) == 0, "alignment (h rows in 16-byte pieces)");
+  { const char* why = tail_refusal(h_seg_stride, wav_seg_stride, B, T); SOPRO_CHECK_ARG(!why, why); }
   return launch_tail16<seanet_tail16_kernel<1, true>, true>(reinterpret_cast<const float*>(h), h_seg_stride, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T,
                                                              (hipStream_t)stream);
 }

@@ -167,6 +167,16 @@ int launch_up(const void* x, int64_t x_seg_stride, const float* w, const float* 
   SOPRO_LAUNCH_CHECK();
 }
 
+// What both entry points check about their strides and T: nullptr, or why the call is refused.
+// T: t0 = (tile0 + it) * UTO of seanet_up128_kernel is a 32-bit int; the walk ends at the first t0 >= T, so t0 < T + UTO and
+// t0 + UTO < T + 128 whatever `tiles` is.  Addresses are 64-bit.
+const char* up_refusal(int64_t x_seg_stride, int64_t out_seg_stride, int32_t B, int32_t T) {
+  if (B > 1 && (x_seg_stride < (int64_t)(T + 1) * UC || out_seg_stride < (int64_t)T * UN))
+    return "segment strides: x holds T + 1 rows of 128 per utterance (one pad row in front), out T rows of 256";
+  if (T > INT32_MAX - 128) return "T must stay at or below 2^31 - 129 rows per utterance (32-bit tile row index)";
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" int sopro_seanet_up_set_tiles(int tiles) {
@@ -181,8 +191,7 @@ extern "C" int sopro_seanet_up128_bf16(const void* x, int64_t x_seg_stride, cons
   SOPRO_CHECK_ARG(x && w && bias && out && B > 0 && T > 0, "bad pointers or sizes");
   SOPRO_CHECK_ARG(aligned16(x) && aligned16(w) && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (x_seg_stride & 7) == 0 && (out_seg_stride & 1) == 0,
                   "x, w 16-byte aligned, x segment stride % 8 == 0 (16-byte row pieces), out 4-byte aligned");
-  SOPRO_CHECK_ARG(B == 1 || (x_seg_stride >= (int64_t)(T + 1) * UC && out_seg_stride >= (int64_t)T * UN),
-                  "segment strides: x holds T + 1 rows of 128 per utterance (one pad row in front), out T rows of 256");
+  { const char* why = up_refusal(x_seg_stride, out_seg_stride, B, T); SOPRO_CHECK_ARG(!why, why); }
   return launch_up<1, true>(x, x_seg_stride, w, bias, out, out_seg_stride, B, T, (hipStream_t)stream);
 }
 
@@ -192,8 +201,7 @@ extern "C" int sopro_seanet_up128_f32(const float* x, int64_t x_seg_stride, cons
   SOPRO_CHECK_ARG(passes == 1 || passes == 3, "passes must be 3 (three-pass split-bf16) or 1 (bf16 mode)");
   SOPRO_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(out) && (x_seg_stride & 3) == 0 && (out_seg_stride & 3) == 0,
                   "x, w, out must be 16-byte aligned with segment strides % 4 == 0");
-  SOPRO_CHECK_ARG(B == 1 || (x_seg_stride >= (int64_t)(T + 1) * UC && out_seg_stride >= (int64_t)T * UN),
-                  "segment strides: x holds T + 1 rows of 128 per utterance (one pad row in front), out T rows of 256");
+  { const char* why = up_refusal(x_seg_stride, out_seg_stride, B, T); SOPRO_CHECK_ARG(!why, why); }
   if (passes == 3) return launch_up<3, false>(x, x_seg_stride, w, bias, out, out_seg_stride, B, T, (hipStream_t)stream);
   return launch_up<1, false>(x, x_seg_stride, w, bias, out, out_seg_stride, B, T, (hipStream_t)stream);
 }

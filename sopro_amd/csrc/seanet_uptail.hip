@@ -484,6 +484,16 @@ int launch_uptail(const void* x, int64_t x_seg_stride, const float* wu, const fl
   SOPRO_LAUNCH_CHECK();
 }
 
+// What both entry points check about their strides and T: nullptr, or why the call is refused.
+// T: S = 4 * T and sidx = s0 + 16 * wave + (lane >> 2) of seanet_uptail_kernel are 32-bit ints; s0 = k * FTS with k <= ntile - 1,
+// so s0 < 4 T + 128 and sidx < 4 T + 256 whatever `tiles` is.
+const char* uptail_refusal(int64_t x_seg_stride, int64_t wav_seg_stride, int32_t B, int32_t T) {
+  if (B > 1 && (x_seg_stride < (int64_t)(T + 1) * FC || wav_seg_stride < (int64_t)4 * T))
+    return "segment strides: x holds T + 1 rows of 128 per utterance (one zero row in front), wav 4 T samples";
+  if (T > (INT32_MAX - 256) / 4) return "T must stay at or below 2^29 - 65 input rows per utterance (32-bit sample index 4 T + 255)";
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" int sopro_seanet_uptail_set_tiles(int tiles) {
@@ -497,8 +507,7 @@ extern "C" int sopro_seanet_uptail_f32(const float* x, int64_t x_seg_stride, con
   SOPRO_CHECK_ARG(x && wu && bu && w1 && b1 && w2 && b2 && wf && wav && B > 0 && T > 0, "bad pointers or sizes");
   SOPRO_CHECK_ARG(passes == 1 || passes == 3, "passes must be 3 (three-pass split-bf16) or 1 (bf16 mode)");
   SOPRO_CHECK_ARG(aligned16(x) && aligned16(wu) && aligned16(w1) && aligned16(w2) && (x_seg_stride & 3) == 0, "x, wu, w1, w2 16-byte aligned, x segment stride % 4 == 0");
-  SOPRO_CHECK_ARG(B == 1 || (x_seg_stride >= (int64_t)(T + 1) * FC && wav_seg_stride >= (int64_t)4 * T),
-                  "segment strides: x holds T + 1 rows of 128 per utterance (one zero row in front), wav 4 T samples");
+  { const char* why = uptail_refusal(x_seg_stride, wav_seg_stride, B, T); SOPRO_CHECK_ARG(!why, why); }
   if (passes == 3) return launch_uptail<3, false>(x, x_seg_stride, wu, bu, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T, (hipStream_t)stream);
   return launch_uptail<1, false>(x, x_seg_stride, wu, bu, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T, (hipStream_t)stream);
 }
@@ -508,7 +517,6 @@ extern "C" int sopro_seanet_uptail_bf16(const void* x, int64_t x_seg_stride, con
                                         int32_t T, void* stream) {
   SOPRO_CHECK_ARG(x && wu && bu && w1 && b1 && w2 && b2 && wf && wav && B > 0 && T > 0, "bad pointers or sizes");
   SOPRO_CHECK_ARG(aligned16(x) && aligned16(wu) && aligned16(w1) && aligned16(w2) && (x_seg_stride & 7) == 0, "x, wu, w1, w2 16-byte aligned, x segment stride % 8 == 0");
-  SOPRO_CHECK_ARG(B == 1 || (x_seg_stride >= (int64_t)(T + 1) * FC && wav_seg_stride >= (int64_t)4 * T),
-                  "segment strides: x holds T + 1 rows of 128 per utterance (one zero row in front), wav 4 T samples");
+  { const char* why = uptail_refusal(x_seg_stride, wav_seg_stride, B, T); SOPRO_CHECK_ARG(!why, why); }
   return launch_uptail<1, true>(x, x_seg_stride, wu, bu, w1, b1, w2, b2, wf, bf, wav, wav_seg_stride, B, T, (hipStream_t)stream);
 }

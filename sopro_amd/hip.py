@@ -848,16 +848,17 @@ def final_conv(h: torch.Tensor, w: torch.Tensor, bias: float, wav: torch.Tensor,
 
 
 def seanet_tail(h: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, wf: torch.Tensor,
-                bf: float, wav: torch.Tensor, *, B: int, T: int, h_seg_stride: int, wav_seg_stride: int) -> None:
-    _check(load().sopro_seanet_tail_f32(ptr(h), h_seg_stride, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(wf), bf, ptr(wav),
-                                        wav_seg_stride, B, T, _stream()), "sopro_seanet_tail_f32")
+                bf: float, wav: torch.Tensor, *, B: int, T: int, h_seg_stride: int, wav_seg_stride: int, passes: int = 3) -> None:
+    """Fused 24 kHz tail of the SEANet decoder (sopro_seanet_tail_p_f32); passes 1 = one MFMA pass on long inputs (bf16 mode)."""
+    _check(load().sopro_seanet_tail_p_f32(ptr(h), h_seg_stride, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(wf), bf, ptr(wav),
+                                          wav_seg_stride, B, T, passes, _stream()), "sopro_seanet_tail_p_f32")
 
 
 def seanet_res128(h: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, out: torch.Tensor, *, B: int,
-                  T: int, h_seg_stride: int, out_seg_stride: int) -> None:
-    """Fused 128-channel residual block of the SEANet decoder + the next layer's ELU (sopro_seanet_res128_f32)."""
-    _check(load().sopro_seanet_res128_f32(ptr(h), h_seg_stride, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(out), out_seg_stride, B, T,
-                                          _stream()), "sopro_seanet_res128_f32")
+                  T: int, h_seg_stride: int, out_seg_stride: int, passes: int = 3) -> None:
+    """Fused 128-channel residual block of the SEANet decoder + the next layer's ELU (sopro_seanet_res128_p_f32)."""
+    _check(load().sopro_seanet_res128_p_f32(ptr(h), h_seg_stride, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(out), out_seg_stride, B, T,
+                                            passes, _stream()), "sopro_seanet_res128_p_f32")
 
 
 def seanet_up128(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, *, B: int, T: int, x_seg_stride: int,

@@ -1109,6 +1109,32 @@ int sopro_align_dp_f32(const float* score, int64_t ld, int64_t bstride, const in
                        int32_t S_cap, void* ws, int64_t ws_bytes, int32_t* path, int64_t path_ld, int32_t* bounds, float* total, int32_t* status,
                        void* stream);
 
+/* Online path: the same recurrence, committed as the frames arrive (streaming word timestamps; DESIGN.md "Word timestamps",
+ * restatement: tests/align_online_ref.py).  Per row b, SOPRO_ALIGN_STATE_WORDS 32-bit words of device state that persist between
+ * calls: state[b] = (c, p, status, e, base) - c int32: the last committed frame, p int32: its text position, status int32, e int32:
+ * the position the last step's backtrack started from, base: the fp32 score of the committed path, as its bits.  Before a row's
+ * first call: (-1, -1, 0, 0, 0.0f).  One call is one step over frames [0, t1s[b]) scored so far, S = slens[b] >= 1 positions,
+ * final = finals[b] != 0, lag >= 0 frames; a = c + 1, n = t1 - a:
+ *   n <= 0, or not final and t1 - 1 - lag < a: the row is left as it is (state and path).
+ *   D[a-1][p] = base, every other entry -inf (p = -1 is a position left of 0, so frame 0 lands on position 0);
+ *   D[t][s] = score[t][s] + max(D[t-1][s], D[t-1][s-1]) for t = a .. t1 - 1 (one fp32 add; from s - 1 only when strictly greater);
+ *   only positions p .. p + (t - c) are finite: one lane per position p + lane, n <= 63 frames.
+ *   e = S - 1 and status 0 when final and D[t1-1][S-1] is finite; else e = the lowest s that maximises D[t1-1][s], status 2 when
+ *   final (the text was not finished), 0 otherwise.  Backtrack from (t1 - 1, e).
+ *   commit frames a .. u, u = t1 - 1 when final, else t1 - 1 - lag: path[b][a..u] is written, base += score[t][path[t]] in frame
+ *   order (equal to D[u][path[u]] bit for bit), c = u, p = path[u].
+ *   n > 63: the row is refused on the device: status = 3 and nothing else is written (the window lives in device memory, so the
+ *   host entry cannot see it; a caller that steps by k frames with lag L never exceeds k + L).
+ * score [B][T_cap][ld] fp32 (finite), t1s / slens / finals int32 [B] (t1 clamped to [0, T_cap], S to S_cap), path int32 [B][path_ld].
+ * Nothing of path before frame a or past frame u is written.  Refused (-2, nothing launched): a NULL pointer, B, T_cap or S_cap <= 0,
+ * S_cap > 2048, ld < S_cap, path_ld < T_cap, lag < 0, with B > 1 a bstride below T_cap * ld.  One launch of one wave per row on
+ * `stream`: D in a register per lane, the neighbour through a lane shift, a frame's decisions one ballot word in LDS; no workspace,
+ * nothing allocated, nothing synchronised. */
+#define SOPRO_ALIGN_STATE_WORDS 5
+#define SOPRO_ALIGN_WINDOW_MAX 63
+int sopro_align_online_f32(const float* score, int64_t ld, int64_t bstride, const int32_t* t1s, const int32_t* slens, const int32_t* finals,
+                           int32_t B, int32_t T_cap, int32_t S_cap, int32_t lag, void* state, int32_t* path, int64_t path_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

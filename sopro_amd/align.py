@@ -6,6 +6,7 @@ monotonic path through them) is defined in DESIGN.md "Word timestamps" and inclu
     Alignment   what the engine knows about one utterance, in frames
     token_spans character range of every token id ``encode_text`` returns (BOS / EOS: empty)
     word_cues   tokens -> words -> sample ranges
+    StreamCues  the same for a path that arrives in committed pieces (``SoproTTS.stream_timed`` -> ``TimedChunk``)
     map_speed   a sample position before the speaking-rate stretch -> after it
     map_pitch   a sample position before the pitch resampler -> after it
 """
@@ -27,7 +28,8 @@ class Alignment:
     ``token_frames[s]``: (first frame, last frame + 1) of text position s; ``total``: the path's log score; ``confidence`` =
     exp(total / T), the geometric mean of the mean attention probability along the path (1 / S for flat maps); ``status`` 0: the
     path is the best monotonic one, 1: no monotonic path exists (fewer frames than text positions, or none) and the frames were
-    spread evenly."""
+    spread evenly, 2 (``stream_timed`` only): the online path ended before the last text position - the positions above
+    ``path[-1]`` have the empty range (T, T); ``total`` is then the score of the path as committed."""
 
     path: List[int]
     token_frames: List[Tuple[int, int]]
@@ -134,6 +136,120 @@ def word_cues(text: str, spans: Sequence[Tuple[int, int]], token_frames: Sequenc
     return cues
 
 
+class TimedChunk(NamedTuple):
+    """One item of ``SoproTTS.stream_timed``: ``wav`` [1, n] on the device (n may be 0), the ``WordCue`` of every word this step
+    closed (samples on the timeline of the concatenated ``wav`` fields), and on the last item ``final=True`` with the utterance's
+    ``Alignment``."""
+    wav: Any
+    words: List[WordCue]
+    final: bool
+    alignment: Optional[Alignment] = None
+
+
+ONLINE_WINDOW_MAX = 63          # frames one step of the online aligner can walk (hip.ALIGN_WINDOW_MAX; kept here like TSM_HS)
+
+
+def check_align_window(lag_frames: int, chunk_frames: int) -> None:
+    """A stream that steps by ``chunk_frames`` at lag ``lag_frames`` hands the online aligner windows of up to their sum."""
+    lag, cf = int(lag_frames), int(chunk_frames)
+    if lag < 0 or cf < 1:
+        raise ValueError(f"lag_frames must be >= 0 and chunk_frames >= 1, got {lag} and {cf}")
+    if lag + cf > ONLINE_WINDOW_MAX:
+        raise ValueError(f"lag_frames + chunk_frames = {lag + cf}: the online aligner walks at most {ONLINE_WINDOW_MAX} uncommitted "
+                         "frames per step")
+
+
+def path_token_frames(path: Sequence[int], n_tokens: int) -> List[Tuple[int, int]]:
+    """(first frame, last frame + 1) per text position of a monotone frame-to-position path (steps of 0 or +1 from position 0);
+    positions the path never reached (an online alignment that ended with status 2) get the empty range (T, T)."""
+    T = len(path)
+    out: List[Tuple[int, int]] = [(T, T)] * int(n_tokens)
+    t = 0
+    while t < T:
+        s, a = int(path[t]), t
+        while t < T and int(path[t]) == s:
+            t += 1
+        if 0 <= s < n_tokens:
+            out[s] = (a, t)
+    return out
+
+
+def _word_tokens(text: str, spans: Sequence[Tuple[int, int]]):
+    """(words, first token, last token) by the membership rule of ``word_cues``."""
+    words = words_of(text)
+    first: List[Optional[int]] = [None] * len(words)
+    last: List[Optional[int]] = [None] * len(words)
+    starts = [a for a, _b in words]
+    for s in range(len(spans)):
+        a, b = int(spans[s][0]), min(int(spans[s][1]), len(text))
+        c = max(a, 0)
+        while c < b and text[c].isspace():
+            c += 1
+        if c >= b:
+            continue
+        wi = bisect.bisect_right(starts, c) - 1
+        if first[wi] is None:
+            first[wi] = s
+        last[wi] = s
+    return words, first, last
+
+
+class StreamCues:
+    """``word_cues`` for a path that arrives in committed pieces (``hip.align_online`` never revises what it committed).  ``feed``
+    takes the next slice of the path and returns the cues of the words it closed, in text order: a token closes when the committed
+    position passes it, or at the final step; a word closes with its last token; a word without tokens follows the word before it
+    at once, as a zero-length cue.  After the final step the concatenated cues equal ``word_cues(text, spans,
+    path_token_frames(whole path, len(spans)))``."""
+
+    def __init__(self, text: str, spans: Sequence[Tuple[int, int]], hop: int = HOP):
+        self.text, self.hop = text, int(hop)
+        self.n_tokens = len(spans)
+        self.words, self.first, self.last = _word_tokens(text, spans)
+        self.frames: List[Optional[Tuple[int, int]]] = [None] * self.n_tokens  # closed tokens only
+        self.T = 0            # committed frames
+        self.pos = -1         # position of the last committed frame
+        self.start = 0        # first frame of position ``pos``
+        self.closed = 0       # tokens [0, closed) are closed
+        self.next_word = 0
+        self.prev_end = 0
+        self.done = False
+
+    def feed(self, path_slice: Sequence[int], final: bool = False) -> List[WordCue]:
+        if self.done:
+            raise ValueError("StreamCues: fed after the final step")
+        for v in path_slice:
+            s = int(v)
+            if s != self.pos:
+                if not (s == self.pos + 1 and 0 <= s < self.n_tokens):
+                    raise ValueError(f"StreamCues: frame {self.T} steps from position {self.pos} to {s}")
+                if self.pos >= 0:
+                    self.frames[self.pos] = (self.start, self.T)
+                self.pos, self.start = s, self.T
+                self.closed = s
+            self.T += 1
+        if final:
+            if self.pos >= 0:
+                self.frames[self.pos] = (self.start, self.T)
+            for s in range(self.pos + 1, self.n_tokens):
+                self.frames[s] = (self.T, self.T)
+            self.closed = self.n_tokens
+            self.done = True
+        out: List[WordCue] = []
+        while self.next_word < len(self.words):
+            k = self.next_word
+            a, b = self.words[k]
+            if self.first[k] is None:
+                st = en = self.prev_end
+            elif self.last[k] < self.closed:
+                st, en = self.frames[self.first[k]][0] * self.hop, self.frames[self.last[k]][1] * self.hop
+            else:
+                break
+            out.append(WordCue(self.text[a:b], a, b, st, en))
+            self.prev_end = en
+            self.next_word += 1
+        return out
+
+
 def map_speed(sample: int, step: int) -> int:
     """A sample position of the unstretched waveform -> its position after ``hip.time_stretch`` at ``step = hip.tsm_step(speed)``:
     (sample * HS * 65536) // step, the arithmetic of ``hip.tsm_out_len``.  Exact for the waveform's length; inside it the stretch
@@ -199,7 +315,7 @@ def refuse_timing(kwargs, what: str) -> None:
     keywords that pass (None / False) are dropped from ``kwargs``."""
     asked = [k for k in TIMING_KEYWORDS if kwargs.get(k) not in (None, False)]
     if asked:
-        raise NotImplementedError(f"{what} has no word timing ({', '.join(asked)}): use synthesize_timed(), synthesize_batch(alignment=[...]) "
-                                  "or synthesize_long(word_cues=True)")
+        raise NotImplementedError(f"{what} has no word timing ({', '.join(asked)}): use stream_timed(), synthesize_timed(), "
+                                  "synthesize_batch(alignment=[...]) or synthesize_long(word_cues=True)")
     for k in TIMING_KEYWORDS:
         kwargs.pop(k, None)

@@ -10,6 +10,9 @@
 //                  keys: one wave, D in a register per lane, the neighbour through a lane shift.  Up to 2048: a double-buffered row
 //                  in LDS, one barrier per frame.  The scores of the next frames are loaded ahead of the recurrence.  One lane walks
 //                  the bits back, then every frame writes its token's boundaries.
+//   align_online - the same recurrence for a stream: one wave per row continues from the last committed cell over the frames that
+//                  arrived since (at most 63, so the reachable band is one wave wide), backtracks from the best end it can see and
+//                  commits everything but the last `lag` frames; the row's state stays in device memory between the calls.
 #include <math.h>
 
 #include "common.h"
@@ -348,6 +351,112 @@ __global__ __launch_bounds__(AL_NT) void align_dp_wide_kernel(const float* __res
   dp_backtrack(T, S, W, tid, AL_NT, bits, pth, bnd);
 }
 
+// The online form: one wave per row walks the frames that arrived since the last commit.  Lane l holds band position p + l (the
+// committed position and what a step per frame can reach from it: at most 64 positions over 63 frames, whatever S is).  The
+// decisions of a frame are one ballot word in LDS; lane 0 walks them back, then every lane stores its frame's position and
+// fetches that cell's score, which lane 0 folds into the committed total in frame order.
+constexpr int ON_WIN = SOPRO_ALIGN_WINDOW_MAX;
+
+__global__ __launch_bounds__(64) void align_online_kernel(const float* __restrict__ score, int64_t ld, int64_t bstride,
+                                                          const int32_t* __restrict__ t1s, const int32_t* __restrict__ slens,
+                                                          const int32_t* __restrict__ finals, int32_t T_cap, int32_t S_cap, int32_t lag,
+                                                          int32_t* __restrict__ state, int32_t* __restrict__ path, int64_t path_ld) {
+  __shared__ unsigned long long bits[ON_WIN];
+  __shared__ int32_t pos[ON_WIN];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int t1 = t1s[b], S = slens[b];
+  t1 = t1 < 0 ? 0 : (t1 > T_cap ? T_cap : t1);
+  S = S > S_cap ? S_cap : S;
+  const bool fin = finals[b] != 0;
+  int32_t* st = state + (int64_t)b * SOPRO_ALIGN_STATE_WORDS;
+  const int c = st[0], p = st[1];
+  const int a = c + 1, n = t1 - a;
+  if (n <= 0 || S <= 0 || c < -1 || p < -1 || p >= S) return;  // (uniform) nothing new, or a state this entry never wrote
+  if (!fin && t1 - 1 - lag < a) return;                          // (uniform) nothing can be committed yet
+  if (n > ON_WIN) {                                              // (uniform) refused: the band would not fit the wave
+    if (lane == 0) st[2] = 3;
+    return;
+  }
+  const float* sc = score + (int64_t)b * bstride;
+  const int s = p + lane;
+  const bool live = s >= 0 && s < S;
+  float d = (lane == 0) ? __int_as_float(st[4]) : -INFINITY;  // the virtual previous row: base at position p
+  float nxt[DP_AHEAD];
+#pragma unroll
+  for (int i = 0; i < DP_AHEAD; ++i) nxt[i] = (live && i < n) ? sc[(int64_t)(a + i) * ld + s] : 0.f;
+  for (int k = 0; k < n; k += DP_AHEAD) {
+    float cur[DP_AHEAD];
+#pragma unroll
+    for (int i = 0; i < DP_AHEAD; ++i) cur[i] = nxt[i];
+#pragma unroll
+    for (int i = 0; i < DP_AHEAD; ++i) {  // the loads of the next group do not depend on the chain below
+      const int kn = k + DP_AHEAD + i;
+      nxt[i] = (live && kn < n) ? sc[(int64_t)(a + kn) * ld + s] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < DP_AHEAD; ++i) {
+      if (k + i < n) {  // (uniform)
+        float left = __shfl_up(d, 1, 64);
+        if (lane == 0) left = -INFINITY;
+        const bool take = live && left > d;
+        const unsigned long long w = __ballot(take);
+        d = live ? cur[i] + (take ? left : d) : -INFINITY;
+        if (lane == 0) bits[k + i] = w;
+      }
+    }
+  }
+  // the end: the last position when the row is final and can reach it, else the best cell of the last frame (lowest position on ties)
+  int e_lane = -1, status = 0;
+  const int last_lane = S - 1 - p;
+  if (fin && last_lane < 64) {
+    const float v = __shfl(d, last_lane, 64);
+    if (v > -INFINITY) e_lane = last_lane;
+  }
+  if (e_lane < 0) {
+    float bv = d;
+    int bi = lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    e_lane = bi;
+    status = fin ? 2 : 0;
+  }
+  const int u = fin ? t1 - 1 : t1 - 1 - lag;  // the last frame this step commits (a <= u <= t1 - 1)
+  __syncthreads();
+  if (lane == 0) {
+    int l = e_lane;
+    for (int k = n - 1; k >= 0; --k) {
+      pos[k] = p + l;
+      l -= (int)((bits[k] >> l) & 1ull);
+    }
+  }
+  __syncthreads();
+  const int nc = u - a + 1;  // committed frames: 1 .. n
+  float v = 0.f;
+  int my = 0;
+  if (lane < nc) {
+    my = pos[lane];
+    v = sc[(int64_t)(a + lane) * ld + my];
+    path[(int64_t)b * path_ld + a + lane] = my;
+  }
+  float base = __int_as_float(st[4]);
+  for (int k = 0; k < nc; ++k) base = base + __shfl(v, k, 64);  // (uniform; frame order, one fp32 add each)
+  const int pu = __shfl(my, nc - 1, 64);
+  if (lane == 0) {
+    st[0] = u;
+    st[1] = pu;
+    st[2] = status;
+    st[3] = p + e_lane;
+    st[4] = __float_as_int(base);
+  }
+}
+
 }  // namespace
 
 int64_t sopro_align_ws_bytes(int32_t B, int32_t T_cap, int32_t S_cap) {
@@ -400,5 +509,19 @@ int sopro_align_dp_f32(const float* score, int64_t ld, int64_t bstride, const in
     hipLaunchKernelGGL(align_dp_wide_kernel, dim3(B), dim3(AL_NT), 0, (hipStream_t)stream, score, ld, bstride, tlens, slens, T_cap, S_cap,
                        static_cast<unsigned long long*>(ws), path, path_ld, bounds, total, status);
   }
+  SOPRO_LAUNCH_CHECK();
+}
+
+int sopro_align_online_f32(const float* score, int64_t ld, int64_t bstride, const int32_t* t1s, const int32_t* slens, const int32_t* finals,
+                           int32_t B, int32_t T_cap, int32_t S_cap, int32_t lag, void* state, int32_t* path, int64_t path_ld, void* stream) {
+  SOPRO_CHECK_ARG(score && t1s && slens && finals && state && path, "every pointer must be non-NULL");
+  SOPRO_CHECK_ARG(B > 0 && T_cap > 0 && S_cap > 0, "B, T_cap, S_cap > 0");
+  SOPRO_CHECK_ARG(S_cap <= AL_SMAX, "S_cap <= 2048");
+  SOPRO_CHECK_ARG(lag >= 0, "lag >= 0");
+  SOPRO_CHECK_ARG(ld >= S_cap && path_ld >= T_cap, "ld >= S_cap and path_ld >= T_cap");
+  SOPRO_CHECK_ARG(B == 1 || bstride >= (int64_t)T_cap * ld, "bstride must cover T_cap rows");
+  SOPRO_CHECK_ARG((reinterpret_cast<uintptr_t>(state) & 3u) == 0, "state must be 4-byte aligned");
+  hipLaunchKernelGGL(align_online_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, score, ld, bstride, t1s, slens, finals, T_cap, S_cap, lag,
+                     static_cast<int32_t*>(state), path, path_ld);
   SOPRO_LAUNCH_CHECK();
 }

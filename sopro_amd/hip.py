@@ -291,6 +291,7 @@ SYMBOLS = {
     "sopro_align_scores_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _f32, C.c_uint32, _f32, _i32, _p, _i64,
                                          _i64, _p]),
     "sopro_align_dp_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "sopro_align_online_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1650,7 +1651,8 @@ class SilenceState(_RowsState):
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----
 ALIGN_S_MAX, ALIGN_DH = 2048, 96
-align_calls = 0  # launches of sopro_align_scores_f32 / sopro_align_dp_f32 by this process: a call that asks for no timing never adds to it
+ALIGN_STATE_WORDS, ALIGN_WINDOW_MAX = 5, 63  # SOPRO_ALIGN_STATE_WORDS / SOPRO_ALIGN_WINDOW_MAX
+align_calls = 0  # launches of sopro_align_scores_f32 / sopro_align_dp_f32 / sopro_align_online_f32 by this process: a call that asks for no timing never adds to it
 
 
 def _align_lens(tlens, slens, B: int, dev):
@@ -1722,6 +1724,58 @@ def align_paths(score: torch.Tensor, tlens, slens, *, path: Optional[torch.Tenso
                                       S_cap, ws.data_ptr(), int(ws.numel() * ws.element_size()), ptr(path, torch.int32), int(path.stride(0)),
                                       ptr(bounds, torch.int32), ptr(total), ptr(status, torch.int32), _stream()), "sopro_align_dp_f32")
     return path, bounds, total, status
+
+
+def align_online_state(B: int, device) -> torch.Tensor:
+    """A fresh online-aligner state: int32 [B, 5] = (c, p, status, e, base bits) = (-1, -1, 0, 0, 0.0f) per row."""
+    st = torch.zeros(int(B), ALIGN_STATE_WORDS, dtype=torch.int32)
+    st[:, :2] = -1
+    return st.to(device)
+
+
+def align_online(score, t1s, slens, finals, lag: int, state, path) -> None:
+    """One step of the online path operator for every row (sopro_align_online_f32): ``score`` fp32 [B, T_cap, S_cap] on the device
+    (rows ``score.stride(1)`` apart) holding frames [0, t1s[b]) of row b, ``slens`` text positions per row, ``finals`` nonzero for rows
+    whose last frame is in, ``lag`` frames held back from the commit; ``state`` int32 [B, 5] (``align_online_state``) and ``path``
+    int32 [B, >= T_cap] are updated in place: frames c + 1 .. u are committed (include/sopro_hip.h).  ``t1s`` / ``slens`` / ``finals``:
+    int32 device vectors, or host sequences (uploaded together).  A row may step over at most 63 uncommitted frames (the committed
+    frontier lives on the device, so a longer window shows as status 3 on a row that is otherwise left as it was; a caller stepping
+    by k frames at lag L never exceeds k + L).  One launch on the current stream."""
+    global align_calls
+    lag = int(lag)
+    if lag < 0:
+        raise SoproHipError(f"align_online: lag must be >= 0, got {lag}")
+    for name, v in (("score", score), ("state", state), ("path", path)):
+        if not isinstance(v, torch.Tensor):
+            raise SoproHipError(f"align_online: {name} must be a tensor on the device")
+    ptr(score)
+    ptr(state, torch.int32)
+    ptr(path, torch.int32)
+    if score.dim() != 3 or (int(score.shape[2]) > 1 and score.stride(2) != 1):
+        raise SoproHipError("align_online: score must be fp32 [B, T_cap, S_cap] with contiguous rows")
+    B, T_cap, S_cap = (int(v) for v in score.shape)
+    if S_cap > ALIGN_S_MAX:
+        raise SoproHipError(f"align_online: at most {ALIGN_S_MAX} text positions, got {S_cap}")
+    if tuple(state.shape) != (B, ALIGN_STATE_WORDS) or not state.is_contiguous():
+        raise SoproHipError(f"align_online: state must be a contiguous int32 [{B}, {ALIGN_STATE_WORDS}]")
+    if path.dim() != 2 or int(path.shape[0]) != B or int(path.shape[1]) < T_cap or path.stride(1) != 1:
+        raise SoproHipError(f"align_online: path must be int32 [{B}, >= {T_cap}] with contiguous rows")
+    dev = score.device
+    with torch.cuda.device(dev):
+        if all(isinstance(v, torch.Tensor) for v in (t1s, slens, finals)):
+            tl, sl, fl = (v.to(dev, torch.int32).contiguous() for v in (t1s, slens, finals))
+        else:
+            host = [[int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)] for v in (t1s, slens, finals)]
+            if any(len(h) != B for h in host):
+                raise SoproHipError(f"align_online: one frame count, one text length and one final flag per row ({B})")
+            all3 = torch.tensor(host, dtype=torch.int32).to(dev)
+            tl, sl, fl = all3[0], all3[1], all3[2]
+        if tl.numel() != B or sl.numel() != B or fl.numel() != B:
+            raise SoproHipError(f"align_online: one frame count, one text length and one final flag per row ({B})")
+        align_calls += 1
+        _check(load().sopro_align_online_f32(ptr(score), int(score.stride(1)), int(score.stride(0)), ptr(tl, torch.int32), ptr(sl, torch.int32),
+                                             ptr(fl, torch.int32), B, T_cap, S_cap, lag, ptr(state, torch.int32), ptr(path, torch.int32),
+                                             int(path.stride(0)), _stream()), "sopro_align_online_f32")
 
 
 def set_host_wait(blocking: bool, device=None) -> None:

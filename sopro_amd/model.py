@@ -832,6 +832,156 @@ class SoproTTSModel:
         return [Alignment(path=hp[b][: lens_t[b]], token_frames=[tuple(v) for v in hb[b][: lens_s[b]]], total=float(ht[b]), status=int(hs[b]))
                 for b in range(B)]
 
+    def align_stream(self, prep: Dict[str, Any], *, max_frames: int, lag_frames: int, chunk_frames: int, heads=None) -> "AlignStream":
+        """Word timing for one utterance while it is generated: see ``AlignStream``."""
+        return AlignStream(self, prep, max_frames=max_frames, lag_frames=lag_frames, chunk_frames=chunk_frames, heads=heads)
+
+
+class AlignStream:
+    """``align_batch`` for a stream (DESIGN.md "Word timestamps", online form).  At open the text keys of every attention layer in
+    use are computed once.  ``step(hist, t1, final)`` replays the AR stack with ``align_batch``'s launch sequence over the window
+    rows [ws, t1), ws = max(0, t0 - (rf_ar - 1)) with t0 the frames scored so far - exact for the rows from t0 on, because the causal
+    depthwise convolution is the stack's only temporal operator -, writes the score rows [t0, t1) into a persistent
+    [1, max_frames + 1, S] buffer (``sopro_align_scores_f32`` with the queries offset to row t0 - ws), runs one
+    ``sopro_align_online_f32`` step and downloads the row's state and path.  The window is padded to a multiple of 8 and to at least
+    16 rows, so that the cross-attention always runs on the kernel ``align_batch`` uses from 16 frames on.  Everything is queued on the
+    model's bulk stream; a step's scratch comes from the model's workspace under ``align.s_*`` names (a step ends with a download, so
+    no step reads another's), the score buffer, the text keys and the state belong to the stream object."""
+
+    def __init__(self, model: "SoproTTSModel", prep: Dict[str, Any], *, max_frames: int, lag_frames: int, chunk_frames: int, heads=None):
+        from .align import check_align_window
+
+        check_align_window(lag_frames, chunk_frames)
+        m, cfg, w, dev, D = model, model.cfg, model.w, model.device, model.D
+        self.m, self.lag, self.chunk = m, int(lag_frames), int(chunk_frames)
+        self.masks = m._align_heads(heads)
+        self.n_sel = sum(bin(v).count("1") for v in self.masks.values())
+        self.layers = [int(i) for i in cfg.ar_xattn_layers]
+        self.last = max(i for i in self.layers if self.masks[i])
+        self.modes = {i: (0 if n == 0 else (2 if n == len(self.layers) - 1 else 1)) for n, i in enumerate(self.layers)}
+        Sp = int(prep["txt_seq"].shape[1])
+        self.S = int(prep["text_lens_host"][0]) if prep.get("text_lens_host") is not None else Sp  # (one utterance's prep: no padding)
+        if int(prep["txt_seq"].shape[0]) != 1 or not 1 <= self.S <= Sp or Sp > hip.ALIGN_S_MAX:
+            raise ValueError(f"AlignStream: one utterance of 1..{hip.ALIGN_S_MAX} text positions, got {tuple(prep['txt_seq'].shape)}")
+        self.Sp = Sp
+        self.cond = prep["cond_ar"]
+        self.Tar = min(int(max_frames) + 1, int(self.cond.shape[1]))
+        self.halo = int(cfg.rf_ar()) - 1
+        self.Wmax = min(max(16, -(-(self.halo + self.chunk) // 8) * 8), max(self.Tar, 1))
+        self.ops = m._align_operands()
+        self.t0 = 0          # frames scored
+        self.c = -1          # frames committed - 1 (the device's ``c`` as of the last download)
+        self.state_host = (-1, -1, 0, 0)
+        self.base = 0.0
+        self.path: List[int] = []
+        get, Wm, Tar = m.ws.get, self.Wmax, self.Tar
+        with m.on_stream(bulk=True):
+            self.tok = get("align.s_tok", (1, Wm), dtype=torch.int32)
+            self.xa, self.xb, self.nb = get("align.s_xa", (Wm, D)), get("align.s_xb", (Wm, D)), get("align.s_n", (Wm, D))
+            self.g, self.f = get("align.s_g", (Wm, D)), get("align.s_f", (Wm, 4 * D))
+            self.q, self.att = get("align.s_q", (Wm, D)), get("align.s_att", (Wm, D))
+            # what lives as long as the stream is the stream's own: a later stream of this engine cannot write into it
+            self.acc = torch.empty(1, Tar, Sp, device=dev)
+            self.out = torch.tensor([-1, -1, 0, 0, 0] + [0] * Tar, dtype=torch.int32).to(dev)  # state | path: one download
+            self.state = self.out[: hip.ALIGN_STATE_WORDS].view(1, hip.ALIGN_STATE_WORDS)
+            self.pathd = self.out[hip.ALIGN_STATE_WORDS:].view(1, Tar)
+            ts = prep["txt_seq"].to(dev).float().contiguous().view(Sp, D)
+            nkv = get("align.s_nkv", (Sp, D))
+            self.kv: Dict[int, torch.Tensor] = {}
+            for i in self.layers:
+                if i > self.last:
+                    break
+                pa = f"ar.x_attns.{i}"
+                self.kv[i] = torch.empty(Sp, 2 * D, device=dev)
+                hip.norm(ts, nkv, w[pa + ".nkv.weight"], rows=Sp, C_=D, eps=RMS_EPS)
+                hip.gemm(nkv, w[pa + ".kv.w"], self.kv[i], M=Sp, N=2 * D, K=D)
+
+    def _scores(self, hist: Sequence[int], t0: int, t1: int, lens: torch.Tensor) -> None:
+        """Score rows [t0, t1) from the window [ws, ws + W) (on the bulk stream; ``lens`` = (t1 - t0, S, ...) on the device)."""
+        m, cfg, w, D, ops = self.m, self.m.cfg, self.m.w, self.m.D, self.ops
+        ws = max(0, t0 - self.halo)
+        W = min(max(16, -(-(t1 - ws) // 8) * 8), self.Wmax)
+        if ws + W > self.Tar:  # (the padding rows must be rows of the conditioning: more left context instead)
+            ws = max(0, self.Tar - W)
+            W = self.Tar - ws
+        if t1 - ws > W:
+            raise ValueError(f"AlignStream: a step of {t1 - t0} frames (opened for {self.chunk})")
+        V, bos = m.V, int(cfg.bos_row)
+        rows = [bos if ws + r == 0 else (min(max(int(hist[ws + r - 1]), 0), V - 1) if ws + r - 1 < t1 else 0) for r in range(W)]
+        self.tok[:, :W].copy_(torch.tensor([rows], dtype=torch.int32), non_blocking=False)
+        xa, xb, nb, g, f, q, att = self.xa, self.xb, self.nb, self.g, self.f, self.q, self.att
+        xb[:W].copy_(self.cond[0, ws: ws + W])
+        hip.codebook_sum(self.tok, 1, ops["col"], ops["off"], ops["wq"], w["cb_embed"], xa, rows=W, D=D, base=xb, alpha=1.0, beta=1.0)
+        ksz = int(cfg.ar_kernel)
+        tl, sl = lens[0:1], lens[1:2]
+        acc = self.acc[:, t0:t1]
+        qo = (t0 - ws) * D
+        x, y = xa, xb
+        kv = None
+        for i, dil in enumerate(cfg.ar_dilations):
+            p = f"ar.blocks.{i}"
+            gw, gb = ops[f"glu.{i}"]
+            hip.norm(x, nb, ops["ones"], rows=W, C_=D, eps=RMS_EPS)
+            hip.gemm(nb, gw, g, M=W, N=2 * D, K=D, bias=gb, epilogue=hip.EPI_GLU)
+            hip.dwconv(g, w[p + ".dw.w"], w[p + ".dw.b"], y, B=1, T=W, C_=D, ksize=ksz, dil=int(dil), left=(ksz - 1) * int(dil), mode=1, res=x)
+            hip.norm(y, nb, ops["ones"], rows=W, C_=D, eps=RMS_EPS)
+            hip.gemm(nb, w[p + ".ff1.w"], f, M=W, N=4 * D, K=D, bias=w[p + ".ff1.b"], epilogue=hip.EPI_GELU)
+            hip.gemm(f, w[p + ".ff2.w"], x, M=W, N=D, K=4 * D, bias=w[p + ".ff2.b"], epilogue=hip.EPI_RES, R=y)
+            if i not in self.masks:
+                continue
+            pa = f"ar.x_attns.{i}"
+            kv = self.kv[i]
+            hip.norm(x, nb, ops["ones"], rows=W, C_=D, eps=RMS_EPS)
+            hip.gemm(nb, w[pa + ".qa.w"], q, M=W, N=D, K=D)
+            hip.align_scores(q, kv, tl, sl, acc, head_mask=self.masks[i], weight=1.0 / self.n_sel, mode=self.modes[i], H=4, ldq=D, ldk=2 * D,
+                             q_bstride=W * D, k_bstride=self.Sp * 2 * D, q_off=qo)
+            if i == self.last:
+                break
+            hip.attention(q, kv, kv, att, B=1, H=4, dh=D // 4, Tq=W, Tk=self.Sp, ldq=D, ldk=2 * D, ldv=2 * D, ldo=D, q_bstride=W * D,
+                          k_bstride=self.Sp * 2 * D, v_bstride=self.Sp * 2 * D, o_bstride=W * D, klens=sl, v_off=D)
+            hip.gemm(att, w[pa + ".o.w"], y, M=W, N=D, K=D, epilogue=hip.EPI_RES, R=x, scale=w[pa + ".gate_scale"])
+            x, y = y, x
+        for i in self.layers:  # (as in align_batch: the last launch finishes the scores)
+            if i > self.last:
+                hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=self.modes[i], H=4, ldq=D, ldk=2 * D, q_bstride=W * D,
+                                 k_bstride=self.Sp * 2 * D, q_off=qo)
+        if len(self.layers) == 1:
+            hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=2, H=4, ldq=D, ldk=2 * D, q_bstride=W * D,
+                             k_bstride=self.Sp * 2 * D, q_off=qo)
+
+    @torch.inference_mode()
+    def step(self, hist: Sequence[int], t1: int, final: bool) -> List[int]:
+        """Frames [0, t1) of the codebook-0 history ``hist`` are in (t1 never decreases; ``final``: no more will come) -> the path
+        positions of the frames this step committed.  ``state_host`` = (c, p, status, e), ``base`` and ``path`` follow."""
+        t1 = min(int(t1), self.Tar)
+        t0 = self.t0
+        if t1 < t0:
+            raise ValueError(f"AlignStream: t1 = {t1} after {t0} frames were scored")
+        if t1 - (self.c + 1) > hip.ALIGN_WINDOW_MAX:
+            raise ValueError(f"AlignStream: {t1 - (self.c + 1)} uncommitted frames, at most {hip.ALIGN_WINDOW_MAX}")
+        if t1 == 0 or (t1 == t0 and not final):
+            return []
+        nw = hip.ALIGN_STATE_WORDS
+        with self.m.on_stream(bulk=True):
+            lens = torch.tensor([t1 - t0, self.S, t1, 1 if final else 0], dtype=torch.int32).to(self.m.device)
+            if t1 > t0:
+                self._scores(hist, t0, t1, lens)
+                self.t0 = t1
+            hip.align_online(self.acc, lens[2:3], lens[1:2], lens[3:4], self.lag, self.state, self.pathd)
+            host = self.out[: nw + t1].cpu()
+        c, p, status, e = (int(v) for v in host[:4].tolist())
+        self.base = float(host[4:5].view(torch.float32)[0])
+        new = host[nw + self.c + 1: nw + c + 1].tolist()
+        self.c, self.state_host = c, (c, p, status, e)
+        self.path += new
+        if final:
+            self.m.align_last = self.scores()  # (as after align_batch: the score matrix of the last timed call)
+        return new
+
+    def scores(self) -> torch.Tensor:
+        """The score rows written so far, [1, t0, S] on the device (a view of the persistent buffer)."""
+        return self.acc[:, : self.t0, : self.S]
+
 
 class _PhaseTimer:
     """Optional per-phase wall-clock (device-synchronised) used by bench.py."""

@@ -95,6 +95,101 @@ class SoproTTSStreamer:
             yield wav
 
 
+    @torch.inference_mode()
+    def stream_timed(self, text: str, spans, *, lag_frames: int = 8, align_heads=None, ref_audio_path: Optional[str] = None,
+                     ref_tokens_tq: Optional[torch.Tensor] = None, ref: Optional[PreparedReference] = None, max_frames: int = 400,
+                     top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
+                     ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None, nar_context_frames: Optional[int] = None,
+                     min_gen_frames: Optional[int] = None, text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                     speed: float = 1.0, pitch: float = 0.0, watermark=None):
+        """``stream`` with word cues (``SoproTTS.stream_timed``): the same sampler draws, chunks and effects chain, and after every
+        chunk's decode one step of ``model.AlignStream`` on the frames generated so far.  Yields ``align.TimedChunk``; the words of an
+        item are those the step closed, mapped through ``speed`` / ``pitch`` like ``synthesize_timed``'s.  The aligner steps at every
+        multiple of ``chunk_frames`` (not final: whether the utterance ends there is only known a frame later) and once more, final,
+        when the generator stops.  The loop is ``stream``'s, written out again rather than shared, so that ``stream`` runs the code
+        it ran before this method existed (``silence`` is not a keyword here: its cut table does not exist chunk by chunk)."""
+        from . import align as A
+        from .effects import Chain, Effects, map_cues
+
+        tts = self.tts
+        fx = Effects.of(speed, pitch, None, watermark)
+        chain = Chain.of(fx, tts.device)
+        model = tts.model
+        ids = text_ids if text_ids is not None else tts.encode_text(text)
+        if len(spans) != int(ids.numel()):
+            raise ValueError(f"token_spans: {len(spans)} spans for {int(ids.numel())} token ids")
+        if ref is None:
+            ref = tts.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
+        prep = model.prepare_conditioning(
+            ids, ref, max_frames=max_frames,
+            style_strength=float(style_strength if style_strength is not None else tts.cfg.style_strength))
+        cf = int(chunk_frames if chunk_frames is not None else self.cfg.chunk_frames)
+        nar_ctx = nar_context_frames if nar_context_frames is not None else self.cfg.nar_context_frames
+        if nar_ctx is None:
+            nar_ctx = int(model.rf_nar())
+        nar_ctx = int(nar_ctx)
+        al = model.align_stream(prep, max_frames=max_frames, lag_frames=lag_frames, chunk_frames=cf, heads=align_heads)
+        cues = A.StreamCues(text, spans, hop=int(tts.codec.mc.frame_samples))
+
+        hist: List[int] = []
+        emitted = 0
+        state = MimiDecodeState()
+        empty = torch.zeros(1, 0, device=tts.device)
+
+        def refine_and_emit(end: int) -> Optional[torch.Tensor]:
+            nonlocal emitted, state
+            if end <= emitted:
+                return None
+            ws = max(0, emitted - nar_ctx)
+            cond_win = prep["cond_ar"][:, ws:end, :]
+            tok_a = torch.as_tensor(hist[ws:end], dtype=torch.long).unsqueeze(0)
+            toks = model.nar_refine(cond_win, tok_a).squeeze(0)
+            wav, state = self.mimi_stream.decode_step(toks[emitted - ws:, :], state)
+            emitted = end
+            return wav if wav.numel() > 0 else None
+
+        for _t, tok, is_eos in model.ar_stream(prep, max_frames=max_frames, top_p=top_p, temperature=temperature,
+                                               anti_loop=anti_loop, min_gen_frames=min_gen_frames, lookahead=cf, seed=seed):
+            if is_eos:
+                break
+            hist.append(int(tok))
+            if len(hist) % cf == 0:
+                wav = chain.feed(refine_and_emit(len(hist)))
+                words = map_cues(cues.feed(al.step(hist, len(hist), False)), fx)
+                if wav is not None or words:
+                    yield A.TimedChunk(wav if wav is not None else empty, words, False)
+        if emitted < len(hist):
+            wav = chain.feed(refine_and_emit(len(hist)))
+            if wav is not None:
+                yield A.TimedChunk(wav, [], False)
+        words = map_cues(cues.feed(al.step(hist, len(hist), True), final=True), fx)
+        wav = chain.flush()
+        # (not the device's word: a final step that finds every frame committed - lag 0, the end on a chunk boundary - changes nothing)
+        status = 0 if (al.path and al.path[-1] == len(spans) - 1) else 2
+        alignment = A.Alignment(path=list(al.path), token_frames=A.path_token_frames(al.path, len(spans)), total=float(al.base), status=status)
+        yield A.TimedChunk(wav if wav is not None else empty, words, True, alignment)
+
+
+@torch.inference_mode()
+def stream_timed(tts, text: str, *, lag_frames: int = 8, token_spans=None, align_heads=None, chunk_frames: int = 6, cache_trim: str = "none",
+                 speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, **kwargs):
+    """New: ``stream`` with word cues as they are committed -> an iterator of ``align.TimedChunk`` (see
+    SoproTTSStreamer.stream_timed).  Everything that can be refused is refused here, before anything runs: ``silence=`` (its cut table
+    does not exist chunk by chunk), ``lag_frames + chunk_frames > 63`` (the online aligner's window), bad effect values, a bad head
+    selection, spans that do not match the text's ids."""
+    from . import align as A
+    from .effects import Effects, refuse
+
+    refuse("stream_timed", silence=silence)
+    A.check_align_window(lag_frames, chunk_frames)
+    Effects.of(speed, pitch, None, watermark)
+    tts.model._align_heads(align_heads)
+    spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(tts.tokenizer, text))
+    streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
+    return streamer.stream_timed(text, spans, lag_frames=lag_frames, align_heads=align_heads, chunk_frames=chunk_frames, speed=speed,
+                                 pitch=pitch, watermark=watermark, **kwargs)
+
+
 @torch.inference_mode()
 def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
            ref: Optional[PreparedReference] = None, chunk_frames: int = 6, cache_trim: str = "none", speed: float = 1.0,

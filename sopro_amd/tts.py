@@ -324,6 +324,23 @@ class SoproTTS:
         refuse_timing(kwargs, "stream")
         return stream(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
+    def stream_timed(self, text: str, *, lag_frames: int = 8, token_spans=None, align_heads=None, speed: float = 1.0, pitch: float = 0.0,
+                     watermark=None, silence=None, chunk_frames: int = 6, **kwargs):
+        """New: ``stream`` with word timestamps as the audio is generated -> an iterator of ``align.TimedChunk(wav, words, final,
+        alignment)``.  The ``wav`` fields ([1, n], n may be 0) concatenate to what ``stream`` yields for the same arguments and
+        ``seed``, bit for bit; ``words`` holds an ``align.WordCue`` for every word the step closed, in text order, samples on the
+        timeline of the concatenated output (through ``speed`` and ``pitch`` with ``synthesize_timed``'s accuracy; the mark moves no
+        cue).  A cue is final when it is yielded: the online aligner (``hip.align_online``) commits a frame once ``lag_frames``
+        later frames are in (default 8, 640 ms: a guess until a trained checkpoint is probed with tools/align_probe.py) and never
+        revises it, so a word is reported about ``lag_frames`` frames after its last frame was generated.  The last item has
+        ``final=True``, the remaining words and the ``align.Alignment`` (``status`` 2: the audio ended before the path reached the last
+        text position; the words left over get empty cues at the end).  ``token_spans`` / ``align_heads``: as in ``synthesize_timed``.
+        ``silence=`` is refused, and so is ``lag_frames + chunk_frames > 63``; other keywords are ``stream``'s."""
+        from .streaming import stream_timed
+
+        return stream_timed(self, text, lag_frames=lag_frames, token_spans=token_spans, align_heads=align_heads, speed=speed, pitch=pitch,
+                            watermark=watermark, silence=silence, chunk_frames=chunk_frames, **kwargs)
+
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",

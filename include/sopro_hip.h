@@ -1135,6 +1135,51 @@ int sopro_align_dp_f32(const float* score, int64_t ld, int64_t bstride, const in
 int sopro_align_online_f32(const float* score, int64_t ld, int64_t bstride, const int32_t* t1s, const int32_t* slens, const int32_t* finals,
                            int32_t B, int32_t T_cap, int32_t S_cap, int32_t lag, void* state, int32_t* path, int64_t path_ld, void* stream);
 
+/* ---- reference denoising: a stationary-noise suppressor on the waveform a voice is cloned from ----------------------------- */
+/* No reference counterpart.  Definition (DESIGN.md "Reference denoising"; numpy restatement: tests/denoise_ref.py), for one row x
+ * of n >= 1 fp32 samples at any scale, N = SOPRO_DN_N, H = SOPRO_DN_H:
+ *   framing    w[i] = sqrt(0.5 (1 - cos(2 pi i / N))) (periodic sqrt-Hann; w^2 sums to 2 over the four frames on a sample);
+ *              F = ceil(n / H) + 3 frames; xp = x behind N - H zeros, zero-extended to F H + N - H; frame f = xp[f H : f H + N] w
+ *   spectrum   X[f, k], k = 0 .. N / 2 (SOPRO_DN_BINS values): the real DFT of frame f; P = |X|^2
+ *   smoothing  S[0] = P[0], S[f] = beta S[f - 1] + (1 - beta) P[f], beta = SOPRO_DN_BETA
+ *   floor      M[f, k] = min S[j, k] over |j - f| <= SOPRO_DN_SPAN, 0 <= j < F (centred: the row is all there);
+ *              Nse = max(bias M, SOPRO_DN_FLOOR)
+ *   gain       gamma = P / Nse; xi[0] = max(gamma[0] - 1, 0), xi[f] = alpha G[f - 1]^2 gamma[f - 1] + (1 - alpha) max(gamma[f] - 1, 0),
+ *              alpha = SOPRO_DN_ALPHA; G = max(xi / (1 + xi), g_min), g_min = 10^(-atten_db / 20)
+ *   synthesis  y = 0.5 sum_f w irdft(G[f] X[f]), frames added in ascending f; the output is y[N - H : N - H + n]
+ *   report     input_db = 10 log10(sum x^2 / n + 1e-20); removed_db = 10 log10((sum (x - y)^2 + 1e-20) / (sum x^2 + 1e-20))
+ * fp32 throughout (the device contracts to FMAs and orders its butterflies its own way: a few ulps of the row's peak); the two
+ * report sums are fp32 per hop of H outputs and float64 across hops, in a fixed order.
+ * wav fp32 [rows] rows row_stride apart (any alignment), out likewise; lens int32 [rows] and params float [rows][2] = (atten_db,
+ * bias) are HOST arrays, read before the call returns: 0 <= atten_db <= 40 and 1 <= bias <= 8, or bias == 0: the row is copied
+ * through bit for bit.  A row of length 0 produces nothing; nothing past lens[b] is read into a result or written in out.
+ * report: NULL, or device float [rows][2] = (input_db, removed_db) (a copied row: its level and -200 or less; an empty one: -200, 0).
+ * ws: sopro_denoise_workspace_bytes(rows, cap) bytes of device memory for any cap >= max(lens), 8-byte aligned (per row and frame:
+ * the spectrum, two minimum tracks, two energy sums; -1: rows <= 0 or cap outside [0, 2^24]).
+ * Refused (-2, nothing launched): a NULL lens, params or ws, rows outside 1 .. 65535, a length outside [0, 2^24], a parameter
+ * outside its range, with rows > 1 a stride below max(lens), ws_bytes too small.
+ * Per group of 64 rows five launches on `stream` - analysis (one wave per frame: 256-point complex radix-4 FFT and the real-input
+ * split), tracking (one lane per row and bin: three walks over the frames), synthesis (the inverse, in place), overlap-add (one
+ * workgroup per hop, four frames gathered in ascending f) and the report; no float atomics, so two calls give the same bits.  The
+ * window and the twiddles are made in float64 on the host and uploaded on a device's first call; later calls copy nothing,
+ * allocate nothing and synchronise nothing. */
+#define SOPRO_DN_N 512
+#define SOPRO_DN_H 128
+#define SOPRO_DN_BINS 257
+#define SOPRO_DN_SPAN 94
+#define SOPRO_DN_BETA 0.7f
+#define SOPRO_DN_ALPHA 0.98f
+#define SOPRO_DN_FLOOR 1e-20f
+#define SOPRO_DN_ATTEN_MIN 0.0f
+#define SOPRO_DN_ATTEN_MAX 40.0f
+#define SOPRO_DN_ATTEN_DEFAULT 15.0f
+#define SOPRO_DN_BIAS_MIN 1.0f
+#define SOPRO_DN_BIAS_MAX 8.0f
+#define SOPRO_DN_BIAS_DEFAULT 3.0f
+int64_t sopro_denoise_workspace_bytes(int32_t rows, int64_t cap);
+int sopro_denoise_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens, const float* params, int32_t rows, float* out,
+                           int64_t out_stride, float* report, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,21 +150,41 @@ class MimiCodec:
         return self._rope
 
     # ------------------------------------------------------------------ reference API
-    def encode_file(self, wav_path: str, *, crop_seconds: Optional[float] = None) -> torch.Tensor:
-        """Reference WAV -> Mimi codes [T, Q] (int64, on the device).  reference: src/sopro/codec/mimi.py:42-63:
-        load (mono) -> energy trim -> resample to the codec rate -> optional centre crop -> MimiModel.encode."""
+    def reference_waveform(self, wav_path: str, *, crop_seconds: Optional[float] = None, denoise=None,
+                           report: Optional[list] = None) -> torch.Tensor:
+        """Reference WAV -> the waveform [N] the encoder sees (fp32, on the device, at the codec rate).  reference:
+        src/sopro/codec/mimi.py:42-63: load (mono) -> energy trim -> resample to the codec rate -> optional centre crop.
+        ``denoise`` (new; a ``sopro_amd.Denoise``): the stationary-noise suppressor of ``hip.denoise`` runs after the resampler, so at
+        the codec rate, and before the crop, so its floor tracker sees the whole clip; ``report``: a list that receives the row's
+        ``DenoiseReport``.  ``denoise=None``: nothing more is launched than before."""
         from . import audio
+        from . import denoise as D
 
+        dn = D.check_denoise(denoise)
+        D.report_sink(report)
         wav, sr = audio.load_audio_file(wav_path)
         wav = audio.trim_silence_energy(wav, sr)
         sr_t = int(self.mc.sampling_rate)
         x = self.resample(torch.from_numpy(np.ascontiguousarray(wav)).to(self.device), sr, sr_t)
+        if dn is not None and x.numel() > 0:
+            with self.on_stream():
+                y = hip.denoise(x.reshape(1, -1), [int(x.numel())], dn, report=report is not None)
+            self.stream.synchronize()
+            if report is not None:
+                y, reps = y
+                report.append(reps[0])
+            x = y.reshape(-1)
         if crop_seconds is not None and crop_seconds > 0:
             fps = float(self.mc.frame_rate)
             hop = int(round(sr_t / fps))
             win_frames = max(1, int(round(crop_seconds * fps)))
             x = audio.center_crop_audio(x, win_frames * hop).contiguous()
-        return self.encode_waveform(x)
+        return x
+
+    def encode_file(self, wav_path: str, *, crop_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
+        """Reference WAV -> Mimi codes [T, Q] (int64, on the device): ``encode_waveform(reference_waveform(...))``, the reference's
+        load -> energy trim -> resample -> (``denoise``) -> optional centre crop -> MimiModel.encode."""
+        return self.encode_waveform(self.reference_waveform(wav_path, crop_seconds=crop_seconds, denoise=denoise, report=report))
 
     @torch.inference_mode()
     def resample(self, wav_n: torch.Tensor, sr_in: int, sr_out: int) -> torch.Tensor:

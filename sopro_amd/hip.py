@@ -292,6 +292,8 @@ SYMBOLS = {
                                          _i64, _p]),
     "sopro_align_dp_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "sopro_align_online_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
+    "sopro_denoise_workspace_bytes": (_i64, [_i32, _i64]),
+    "sopro_denoise_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1647,6 +1649,55 @@ class SilenceState(_RowsState):
             self.cuts[b] += cuts[b]
         self._ended = bool(flush)
         return out[:, : max(got)], got
+
+
+# ---- reference denoising (sopro_denoise_*; definition in include/sopro_hip.h, numpy restatement in tests/denoise_ref.py; parameters in denoise.py) ----
+DN_N, DN_H, DN_BINS, DN_SPAN = 512, 128, 257, 94
+denoise_calls = 0  # calls of sopro_denoise_rows_f32 by this process: the denoise=None paths never add to it
+
+
+def denoise(wav: torch.Tensor, lens, params, *, out: Optional[torch.Tensor] = None, report: bool = False):
+    """The stationary-noise suppressor on the rows of a padded batch (sopro_denoise_rows_f32): ``wav`` fp32 [rows, >= max(lens)] on
+    the device (rows ``wav.stride(0)`` apart, any alignment), ``lens`` valid samples per row, ``params`` one ``Denoise`` or None, or
+    one per row -> out [rows, max(lens)], row b valid for lens[b] samples; a row whose ``Denoise`` is None comes back bit for bit.
+    Five launches per 64 rows on the current stream and no synchronisation (the lengths and parameters are host values that travel
+    as kernel arguments).  ``report=True`` -> (out, [DenoiseReport or None per row]), which costs one small host copy.  ``out``: a
+    [rows, >= max(lens)] fp32 buffer to write into (nothing past a row's length is touched).  All None: nothing is launched and
+    ``wav[:, :max(lens)]`` is returned as it is."""
+    from . import denoise as D
+
+    global denoise_calls
+    lens_h = _lens_list(lens)
+    rows = len(lens_h)
+    _check_rows(wav, lens_h, "denoise")
+    dns = D.per_row(params, rows, "params")
+    cap = max(lens_h, default=0)
+    _out_buffer(out, rows, cap, "denoise")
+    if rows == 0 or all(d is None for d in dns):
+        none = [None] * rows
+        if out is None:
+            return (wav[:, :cap], none) if report else wav[:, :cap]
+        out[:, :cap].copy_(wav[:, :cap])  # (a caller that asked for its own buffer gets the rows there)
+        return (out[:, :cap], none) if report else out[:, :cap]
+    dev = wav.device
+    if out is None:
+        out = torch.empty(rows, max(1, cap), dtype=torch.float32, device=dev)
+    lib = load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.sopro_denoise_workspace_bytes(rows, cap))
+        if ws_bytes < 0:
+            raise SoproHipError(f"denoise: {rows} rows of up to {cap} samples are outside the operator's range")
+        ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.int64, device=dev)
+        rep = torch.empty(rows, 2, dtype=torch.float32, device=dev) if report else None
+        lens_c = (C.c_int32 * rows)(*lens_h)
+        par_c = (C.c_float * (2 * rows))(*[v for d in dns for v in ((d.atten_db, d.bias) if d is not None else (0.0, 0.0))])
+        denoise_calls += 1
+        _check(lib.sopro_denoise_rows_f32(ptr(wav) if cap > 0 else None, int(wav.stride(0)), lens_c, par_c, rows, ptr(out) if cap > 0 else None,
+                                          int(out.stride(0)), ptr(rep), ws.data_ptr(), ws_bytes, _stream()), "sopro_denoise_rows_f32")
+        if not report:
+            return out[:, :cap]
+        vals = rep.cpu().tolist()
+    return out[:, :cap], [D.DenoiseReport(float(v[0]), float(v[1])) if d is not None else None for v, d in zip(vals, dns)]
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

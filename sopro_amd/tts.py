@@ -87,18 +87,27 @@ class SoproTTS:
 
     @torch.inference_mode()
     def encode_speaker(self, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
-                       ref_seconds: Optional[float] = None) -> torch.Tensor:
+                       ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
         """reference: src/sopro/model.py:457-475 -> the voice's speaker vector [sv_student_dim] (Token2SV over the cropped
-        reference tokens; the same vector ``prepare_reference`` stores as ``sv_ref``)."""
-        ref = self.encode_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
+        reference tokens; the same vector ``prepare_reference`` stores as ``sv_ref``).  ``denoise``, ``report``: as in
+        ``encode_reference``."""
+        ref = self.encode_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
+                                    report=report)
         ref_btq = ref.unsqueeze(0)
         lengths = torch.tensor([int(ref_btq.size(1))], dtype=torch.long)
         return self.model.token2sv(ref_btq, lengths=lengths).squeeze(0).detach()
 
     @torch.inference_mode()
     def encode_reference(self, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
-                         ref_seconds: Optional[float] = None) -> torch.Tensor:
-        """reference: src/sopro/model.py:477-514 (token path only; audio -> tokens needs the Mimi encoder)."""
+                         ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
+        """reference: src/sopro/model.py:477-514 (token path only; audio -> tokens needs the Mimi encoder).  ``denoise`` (new; a
+        ``sopro_amd.Denoise``): the reference waveform goes through the stationary-noise suppressor before it is cropped and encoded
+        (``MimiCodec.reference_waveform``); ``report``: a list used as a sink, it receives one ``DenoiseReport``.  With
+        ``ref_tokens_tq`` there is no waveform: ``denoise`` other than None is refused."""
+        from . import denoise as D
+
+        D.report_sink(report)
+        D.refuse_without_waveform(denoise, "encode_reference", ref_tokens_tq=ref_tokens_tq)
         if ref_tokens_tq is None and ref_audio_path is None:  # model.py:486-493
             raise RuntimeError("SoproTTS requires a reference. Provide ref_audio_path=... or ref_tokens_tq=...")
         if ref_tokens_tq is not None and ref_audio_path is not None:
@@ -106,7 +115,7 @@ class SoproTTS:
         if ref_seconds is None:
             ref_seconds = 12.0  # model.py:495-496
         if ref_tokens_tq is None:
-            return self.codec.encode_file(ref_audio_path, crop_seconds=ref_seconds if ref_seconds > 0 else None)
+            return self.codec.encode_file(ref_audio_path, crop_seconds=ref_seconds if ref_seconds > 0 else None, denoise=denoise, report=report)
         ref = ref_tokens_tq.long()
         if ref_seconds and ref_seconds > 0:
             fps = float(self.cfg.mimi_fps)
@@ -119,9 +128,10 @@ class SoproTTS:
 
     @torch.inference_mode()
     def prepare_reference(self, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
-                          ref_seconds: Optional[float] = None) -> PreparedReference:
-        """reference: src/sopro/model.py:516-529"""
-        ref = self.encode_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
+                          ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> PreparedReference:
+        """reference: src/sopro/model.py:516-529.  ``denoise``, ``report`` (new): as in ``encode_reference``."""
+        ref = self.encode_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
+                                    report=report)
         return self.model.prepare_reference(ref)
 
     @torch.inference_mode()
@@ -130,17 +140,22 @@ class SoproTTS:
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
                    seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None,
-                   silence=None) -> torch.Tensor:
+                   silence=None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
         draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed``, ``pitch``, ``silence``,
-        ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched."""
+        ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched.
+        ``denoise``, ``report`` (new): the input side, forwarded to ``prepare_reference``; with ``ref`` or ``ref_tokens_tq`` there is
+        no waveform to clean and ``denoise`` other than None is refused."""
+        from . import denoise as D
         from . import effects
 
         fx = effects.Effects.of(speed, pitch, silence, watermark)
+        D.refuse_without_waveform(denoise, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
         text_ids = self.encode_text(text)
         if ref is None:
-            ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
+            ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
+                                         report=report)
         tokens = self.model.generate_tokens(
             text_ids, ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
             style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
@@ -276,7 +291,7 @@ class SoproTTS:
                          ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
                          top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                          ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
-                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None):
+                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None):
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
@@ -284,17 +299,21 @@ class SoproTTS:
         ``pitch`` and ``silence`` (``effects.map_cues`` has their accuracy); the mark changes no length, so it moves no cue.
         ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
-        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12)."""
+        ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12).  ``denoise``,
+        ``report``: as in ``synthesize``."""
         from . import align as A
+        from . import denoise as D
         from . import effects
 
         fx = effects.Effects.of(speed, pitch, silence, watermark)
+        D.refuse_without_waveform(denoise, "synthesize_timed", ref=ref, ref_tokens_tq=ref_tokens_tq)
         text_ids = self.encode_text(text)
         spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
         if len(spans) != int(text_ids.numel()):
             raise ValueError(f"token_spans: {len(spans)} spans for {int(text_ids.numel())} token ids")
         if ref is None:
-            ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds)
+            ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
+                                         report=report)
         sink: list = []
         tokens = self.model.generate_tokens_batch(
             [text_ids], [ref], max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
@@ -317,7 +336,8 @@ class SoproTTS:
         """reference: src/sopro/model.py:577-580.  ``speed``, ``pitch``, ``silence``, ``watermark`` (new): every decoded chunk goes
         through the chunked chain of ``sopro_amd.effects`` and what is ready is yielded as [1, n] (with a watermark a chunk comes out
         up to 1440 samples short and the rest follows); the concatenation is ``synthesize``'s chain over the plain stream's
-        concatenation, bit for bit (see streaming.SoproTTSStreamer.stream)."""
+        concatenation, bit for bit (see streaming.SoproTTSStreamer.stream).  ``denoise=``, ``report=`` (keywords of
+        ``prepare_reference``) clean the reference waveform; with ``ref`` or ``ref_tokens_tq`` ``denoise`` is refused here."""
         from .align import refuse_timing
         from .streaming import stream
 
@@ -335,7 +355,8 @@ class SoproTTS:
         revises it, so a word is reported about ``lag_frames`` frames after its last frame was generated.  The last item has
         ``final=True``, the remaining words and the ``align.Alignment`` (``status`` 2: the audio ended before the path reached the last
         text position; the words left over get empty cues at the end).  ``token_spans`` / ``align_heads``: as in ``synthesize_timed``.
-        ``silence=`` is refused, and so is ``lag_frames + chunk_frames > 63``; other keywords are ``stream``'s."""
+        ``silence=`` is refused, and so is ``lag_frames + chunk_frames > 63``; other keywords are ``stream``'s (``denoise=`` and
+        ``report=`` among them)."""
         from .streaming import stream_timed
 
         return stream_timed(self, text, lag_frames=lag_frames, token_spans=token_spans, align_heads=align_heads, speed=speed, pitch=pitch,
@@ -377,7 +398,7 @@ class SoproTTS:
         between sentences are untouched by the squeeze; the pauses are divided by ``speed`` and not touched by ``pitch``.
         ``watermark``: the batches run unmarked and the joined waveform is marked in one launch, so the carrier's phase is continuous
         across the segments (``parts`` stay unmarked).  Full parameter list:
-        ``longform.synthesize_long``."""
+        ``longform.synthesize_long`` (``denoise=`` and ``report=`` among them: the input side, as in ``synthesize``)."""
         from .longform import synthesize_long
 
         return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
@@ -391,11 +412,13 @@ class SoproTTS:
         and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit.
         ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
         from .align import refuse_timing
+        from .denoise import refuse_without_waveform
         from .effects import Effects
         from .longform import stream_long
 
         refuse_timing(kwargs, "stream_long")
         Effects.of(speed, pitch, silence, watermark)  # (refused here, not at the first piece)
+        refuse_without_waveform(kwargs.get("denoise"), "stream_long", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
         return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
     def detect_watermark(self, wav, key: int):

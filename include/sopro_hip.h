@@ -1180,6 +1180,63 @@ int64_t sopro_denoise_workspace_bytes(int32_t rows, int64_t cap);
 int sopro_denoise_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens, const float* params, int32_t rows, float* out,
                            int64_t out_stride, float* report, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- reference crop selection: the window of a reference waveform with the most speech and the least clipping -------------- */
+/* No reference counterpart (the reference takes the centre crop whatever is in it).  Definition (DESIGN.md "Reference crop
+ * selection"; numpy restatement: tests/crop_ref.py), for one row x of n fp32 samples at the codec rate and a window of W samples,
+ * W a positive multiple of H = SOPRO_CROP_H (10 ms at 24 kHz):
+ *   short rows n <= W: the row comes back bit for bit, start = 0, out_len = n (what the centre crop does); the report is computed
+ *              with o = 0 and one window over all F = n / H blocks (F may be 0: an empty report with level_db = -200)
+ *   grid       s_c = (n - W) / 2 (the centre crop's start), o = s_c mod H, F = (n - o) / H complete blocks, block f =
+ *              x[o + f H : o + (f + 1) H]; Wb = W / H; candidates k = 0 .. F - Wb, the window of k starts at sample o + k H;
+ *              k_c = (s_c - o) / H is the centre crop itself and always a candidate
+ *   features   e[f] = sum x^2 over the block; c[f] = 1 if any |x| >= clip_level in the block (clip_level as fp32), else 0
+ *   threshold  Emax = max e; Emin = min over f of (e[f] + .. + e[f + 4]) / 5 for F >= SOPRO_CROP_SMOOTH, else min e (a 50 ms floor:
+ *              one quiet block between syllables does not set it); thr = max(Emax 10^(-range_db / 10), Emin 10^(margin_db / 10));
+ *              a[f] = e[f] > thr (strict: an all-zero row and a constant-level row have no active block)
+ *   score      score[k] = sum over the window's blocks of a[f] - clip_weight c[f], an integer
+ *   pick       the largest score; ties by the smallest |k - k_c|, then by the smaller k: a row on which the search has no
+ *              preference gets exactly the centre crop, start = s_c (not a multiple of H in general)
+ *   output     out[0 : W] = x[start : start + W], bit for bit; out_len = W
+ *   report     SOPRO_CROP_REPORT_WORDS int32 words per row: start, active and clipped blocks of the chosen window, the same two
+ *              counts of the centre window, active blocks of the row, F, and (the bits of a float) level_db = 10 log10(sum of e
+ *              over the chosen window / W + 1e-20)
+ * The device computes e[f] in fp32 (a lane adds its four squares in ascending sample order, then one fixed cross-lane tree: within
+ * 240 x 2^-24 of the exact sum, relative) and the threshold in fp32; everything after a[f] is integer and exact.  The level adds
+ * the fp32 e[f] in float64, in a fixed order.
+ * wav fp32 [rows] rows row_stride apart (any alignment); out [rows] rows out_stride apart, must not overlap wav; lens int32 [rows]
+ * and params float [rows][4] = (range_db, margin_db, clip_level, clip_weight) are HOST arrays, read before the call returns:
+ * 6 <= range_db <= 80, 0 <= margin_db <= 40, 0 < clip_level <= 8, clip_weight an integer in 0 .. 64; or clip_level == 0: the row
+ * is not searched, it comes back as its first min(n, W) samples with start = 0 and an empty report.  Nothing past min(lens[b], W) of
+ * an output row is written, nothing past lens[b] is read.
+ * starts: device int32 [rows].  report: NULL, or device int32 [rows][SOPRO_CROP_REPORT_WORDS].  blocks: NULL, or device 32-bit words
+ * [rows][2][max(lens) / H] (for tests): per row e[f] as float, then one flag word per block (bit 0 active, bit 1 clipped); blocks
+ * f >= F of a row, and all of a row that is not searched, are left as they were.
+ * ws: sopro_crop_workspace_bytes(rows, cap) bytes of device memory for any cap >= max(lens), 4-byte aligned (per row and block: e,
+ * the flags, the prefix sum; -1: rows <= 0 or cap outside [0, 2^24]).
+ * Refused (-2, nothing launched): a NULL lens, params, starts or ws, rows outside 1 .. 65535, a length outside [0, 2^24], win not a
+ * positive multiple of H, a parameter outside its range, with rows > 1 a stride below max(lens) (out: below min(max(lens), W)),
+ * ws_bytes too small.
+ * Per group of 64 rows three launches on `stream` - blocks (one wave per block), pick (one workgroup per row: the threshold, a
+ * chunked integer prefix sum of a - clip_weight c over any F, a max-reduction over the candidates on the key (score, -|k - k_c|,
+ * -k)), gather (reads starts from device memory); no float atomics, so a row has the same bits alone and in a batch and two calls
+ * give the same bits.  A call copies nothing to the host, allocates nothing and synchronises nothing. */
+#define SOPRO_CROP_H 240
+#define SOPRO_CROP_SMOOTH 5
+#define SOPRO_CROP_REPORT_WORDS 8
+#define SOPRO_CROP_RANGE_MIN 6.0f
+#define SOPRO_CROP_RANGE_MAX 80.0f
+#define SOPRO_CROP_RANGE_DEFAULT 30.0f
+#define SOPRO_CROP_MARGIN_MIN 0.0f
+#define SOPRO_CROP_MARGIN_MAX 40.0f
+#define SOPRO_CROP_MARGIN_DEFAULT 10.0f
+#define SOPRO_CROP_LEVEL_MAX 8.0f
+#define SOPRO_CROP_LEVEL_DEFAULT 0.999f
+#define SOPRO_CROP_WEIGHT_MAX 64
+#define SOPRO_CROP_WEIGHT_DEFAULT 4
+int64_t sopro_crop_workspace_bytes(int32_t rows, int64_t cap);
+int sopro_crop_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens, const float* params, int32_t rows, int32_t win, float* out,
+                        int64_t out_stride, int32_t* starts, int32_t* report, void* blocks, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

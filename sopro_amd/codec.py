@@ -151,17 +151,24 @@ class MimiCodec:
 
     # ------------------------------------------------------------------ reference API
     def reference_waveform(self, wav_path: str, *, crop_seconds: Optional[float] = None, denoise=None,
-                           report: Optional[list] = None) -> torch.Tensor:
+                           report: Optional[list] = None, crop=None) -> torch.Tensor:
         """Reference WAV -> the waveform [N] the encoder sees (fp32, on the device, at the codec rate).  reference:
         src/sopro/codec/mimi.py:42-63: load (mono) -> energy trim -> resample to the codec rate -> optional centre crop.
         ``denoise`` (new; a ``sopro_amd.Denoise``): the stationary-noise suppressor of ``hip.denoise`` runs after the resampler, so at
         the codec rate, and before the crop, so its floor tracker sees the whole clip; ``report``: a list that receives the row's
-        ``DenoiseReport``.  ``denoise=None``: nothing more is launched than before."""
+        ``DenoiseReport``.  ``denoise=None``: nothing more is launched than before.
+        ``crop`` (new; a ``sopro_amd.SpeechCrop``): the window of ``crop_seconds`` comes from ``hip.speech_crop`` (the most speech,
+        the least clipping, the centre crop on a tie) instead of the centre; it runs after the denoiser, and ``report`` receives its
+        ``CropReport`` after the ``DenoiseReport``.  Without a window (``crop_seconds`` None or <= 0) ``crop`` is refused.
+        ``crop=None``: the centre crop, and nothing more is launched than before."""
         from . import audio
+        from . import crop as CR
         from . import denoise as D
 
         dn = D.check_denoise(denoise)
         D.report_sink(report)
+        cr = CR.check_crop(crop)
+        CR.refuse_without_window(cr, "reference_waveform", crop_seconds)
         wav, sr = audio.load_audio_file(wav_path)
         wav = audio.trim_silence_energy(wav, sr)
         sr_t = int(self.mc.sampling_rate)
@@ -178,13 +185,22 @@ class MimiCodec:
             fps = float(self.mc.frame_rate)
             hop = int(round(sr_t / fps))
             win_frames = max(1, int(round(crop_seconds * fps)))
-            x = audio.center_crop_audio(x, win_frames * hop).contiguous()
+            if cr is not None and x.numel() > 0:
+                with self.on_stream():
+                    got = hip.speech_crop(x.reshape(1, -1), [int(x.numel())], cr, win_frames * hop, report=report is not None)
+                self.stream.synchronize()
+                if report is not None:
+                    report.append(got[2][0])
+                x = got[0].reshape(-1)[: got[1][0]].contiguous()
+            else:
+                x = audio.center_crop_audio(x, win_frames * hop).contiguous()
         return x
 
-    def encode_file(self, wav_path: str, *, crop_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
+    def encode_file(self, wav_path: str, *, crop_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None,
+                    crop=None) -> torch.Tensor:
         """Reference WAV -> Mimi codes [T, Q] (int64, on the device): ``encode_waveform(reference_waveform(...))``, the reference's
-        load -> energy trim -> resample -> (``denoise``) -> optional centre crop -> MimiModel.encode."""
-        return self.encode_waveform(self.reference_waveform(wav_path, crop_seconds=crop_seconds, denoise=denoise, report=report))
+        load -> energy trim -> resample -> (``denoise``) -> optional crop (the centre, or ``crop``'s window) -> MimiModel.encode."""
+        return self.encode_waveform(self.reference_waveform(wav_path, crop_seconds=crop_seconds, denoise=denoise, report=report, crop=crop))
 
     @torch.inference_mode()
     def resample(self, wav_n: torch.Tensor, sr_in: int, sr_out: int) -> torch.Tensor:

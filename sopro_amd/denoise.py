@@ -84,4 +84,4 @@ def refuse_without_waveform(dn, what: str, **given) -> None:
 
 def report_sink(report) -> None:
     if report is not None and not isinstance(report, list):
-        raise TypeError(f"report must be a list (it receives one DenoiseReport) or None, got {type(report).__name__}")
+        raise TypeError(f"report must be a list (it receives the DenoiseReport, then the CropReport, of what was asked for) or None, got {type(report).__name__}")

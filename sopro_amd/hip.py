@@ -294,6 +294,8 @@ SYMBOLS = {
     "sopro_align_online_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
     "sopro_denoise_workspace_bytes": (_i64, [_i32, _i64]),
     "sopro_denoise_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _i64, _p]),
+    "sopro_crop_workspace_bytes": (_i64, [_i32, _i64]),
+    "sopro_crop_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1698,6 +1700,78 @@ def denoise(wav: torch.Tensor, lens, params, *, out: Optional[torch.Tensor] = No
             return out[:, :cap]
         vals = rep.cpu().tolist()
     return out[:, :cap], [D.DenoiseReport(float(v[0]), float(v[1])) if d is not None else None for v, d in zip(vals, dns)]
+
+
+# ---- reference crop selection (sopro_crop_*; definition in include/sopro_hip.h, numpy restatement in tests/crop_ref.py; parameters in crop.py) ----
+CROP_H, CROP_SMOOTH, CROP_REPORT_WORDS = 240, 5, 8
+crop_calls = 0  # calls of sopro_crop_rows_f32 by this process: the crop=None paths never add to it
+
+
+def speech_crop(wav: torch.Tensor, lens, params, win: int, *, out: Optional[torch.Tensor] = None, report: bool = False, blocks: bool = False):
+    """The window of ``win`` samples with the most speech and the least clipping of every row of a padded batch
+    (sopro_crop_rows_f32): ``wav`` fp32 [rows, >= max(lens)] on the device (rows ``wav.stride(0)`` apart, any alignment), ``lens``
+    valid samples per row, ``params`` one ``SpeechCrop`` or None, or one per row, ``win`` a positive multiple of 240 ->
+    (out[:, :min(max(lens), win)], out_lens): row b holds ``wav[b, start : start + out_lens[b]]`` bit for bit, out_lens[b] =
+    min(lens[b], win).  A row no longer than ``win`` comes back whole; a row whose ``SpeechCrop`` is None is not searched and comes
+    back as its first out_lens[b] samples.  Three launches per 64 rows on the current stream and no synchronisation (the lengths and
+    parameters are host values that travel as kernel arguments; the gather reads the chosen starts from device memory).
+    ``report=True`` appends [CropReport or None per row], which costs one small host copy; ``blocks=True`` appends the per-block
+    features [(e float32 [F], flags int32 [F]: bit 0 active, bit 1 clipped) or None per row], for tests.  ``out``: a [rows, >=
+    min(max(lens), win)] fp32 buffer to write into, not overlapping ``wav`` (nothing past a row's out_lens is touched).  All None:
+    nothing is launched and ``wav[:, :min(max(lens), win)]`` is returned as it is."""
+    from . import crop as CR
+
+    global crop_calls
+    lens_h = _lens_list(lens)
+    rows = len(lens_h)
+    _check_rows(wav, lens_h, "speech_crop")
+    crs = CR.per_row(params, rows, "params")
+    win = int(win)
+    if win <= 0 or win % CROP_H:
+        raise SoproHipError(f"speech_crop: win must be a positive multiple of {CROP_H}, got {win}")
+    cap = max(lens_h, default=0)
+    width = min(cap, win)
+    out_lens = [min(n, win) for n in lens_h]
+    _out_buffer(out, rows, width, "speech_crop")
+    extra = ([[None] * rows] if report else []) + ([[None] * rows] if blocks else [])
+    if rows == 0 or all(c is None for c in crs):
+        if out is None:
+            return (wav[:, :width], out_lens, *extra)
+        out[:, :width].copy_(wav[:, :width])  # (a caller that asked for its own buffer gets the rows there)
+        return (out[:, :width], out_lens, *extra)
+    dev = wav.device
+    if out is None:
+        out = torch.empty(rows, max(1, width), dtype=torch.float32, device=dev)
+    lib = load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.sopro_crop_workspace_bytes(rows, cap))
+        if ws_bytes < 0:
+            raise SoproHipError(f"speech_crop: {rows} rows of up to {cap} samples are outside the operator's range")
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.int32, device=dev)
+        starts = torch.empty(rows, dtype=torch.int32, device=dev)
+        rep = torch.empty(rows, CROP_REPORT_WORDS, dtype=torch.int32, device=dev) if report else None
+        fc = cap // CROP_H
+        blk = torch.zeros(rows, 2, max(1, fc), dtype=torch.int32, device=dev) if blocks else None
+        lens_c = (C.c_int32 * rows)(*lens_h)
+        par_c = (C.c_float * (4 * rows))(*[v for c in crs for v in ((c.range_db, c.margin_db, c.clip_level, float(c.clip_weight))
+                                                                       if c is not None else (0.0, 0.0, 0.0, 0.0))])
+        crop_calls += 1
+        _check(lib.sopro_crop_rows_f32(ptr(wav) if cap > 0 else None, int(wav.stride(0)), lens_c, par_c, rows, win, ptr(out) if cap > 0 else None,
+                                       int(out.stride(0)), ptr(starts, torch.int32), ptr(rep, torch.int32), ptr(blk, torch.int32), ws.data_ptr(),
+                                       ws_bytes, _stream()), "sopro_crop_rows_f32")
+        res = [out[:, :width], out_lens]
+        if report:
+            words = rep.cpu()
+            level = words[:, CROP_REPORT_WORDS - 1].contiguous().view(torch.float32).tolist()
+            res.append([CR.CropReport(*[int(v) for v in w[: CROP_REPORT_WORDS - 1]], float(lv)) if c is not None else None
+                        for w, lv, c in zip(words.tolist(), level, crs)])
+        if blocks:
+            host, feats = blk.cpu(), []
+            for b, (n, c) in enumerate(zip(lens_h, crs)):
+                F = (n - (((n - win) // 2) % CROP_H if n > win else 0)) // CROP_H
+                feats.append((host[b, 0, :F].contiguous().view(torch.float32).numpy().copy(), host[b, 1, :F].numpy().copy()) if c is not None else None)
+            res.append(feats)
+    return tuple(res)
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

@@ -207,15 +207,17 @@ def _groups(tts, segs: List[Segment], groups: List[int], *, ref, max_frames, top
         k0 += g
 
 
-def _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise=None, report=None):
+def _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise=None, report=None, crop=None):
+    from .crop import refuse_without_waveform as crop_refuse_without_waveform
     from .denoise import refuse_without_waveform
 
     refuse_without_waveform(denoise, "long-form synthesis", ref=ref, ref_tokens_tq=ref_tokens_tq)
+    crop_refuse_without_waveform(crop, "long-form synthesis", ref=ref, ref_tokens_tq=ref_tokens_tq)
     segs = split_text(text, max_chars=max_chars)
     groups = group_plan(len(segs), plan, max_rows)
     if segs and ref is None:  # the voice is prepared once for the whole text
         ref = tts.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                    report=report)
+                                    report=report, crop=crop)
     return segs, groups, ref
 
 
@@ -225,14 +227,14 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
                     keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None,
-                    pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None) -> LongformResult:
+                    pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
     (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k, after ``effects.map_cues`` has
     taken it through its row's rate, pitch and cut table).  ``token_spans``: a callable text -> [(start, end)] per token id for
     tokenizers that give no character offsets; ``align_heads``: the (layer, head) pairs to average.  ``watermark``: the batches get no
     mark (parts stay unmarked); the joined waveform is marked in one launch, so the carrier's phase runs on across the segments and no
-    cue moves.  ``denoise``, ``report``: the input side, forwarded to ``prepare_reference`` (refused with ``ref`` or ``ref_tokens_tq``)."""
+    cue moves.  ``denoise``, ``crop``, ``report``: the input side, forwarded to ``prepare_reference`` (refused with ``ref`` or ``ref_tokens_tq``)."""
     import dataclasses
 
     import torch
@@ -245,7 +247,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     if token_spans is not None and not callable(token_spans):
         raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
     spans_of = token_spans if token_spans is not None else (lambda t: A.token_spans(tts.tokenizer, t))
-    segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise, report)
+    segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise, report, crop)
     if not segs:
         return LongformResult(torch.zeros(1, 1, 0, device=tts.device), [], [], [] if keep_parts else None, [] if keep_parts else None,
                               [] if word_cues else None)
@@ -281,17 +283,17 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                 max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                 fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0,
-                pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None) -> Iterator[Any]:
+                pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None) -> Iterator[Any]:
     """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``).
     ``watermark``: every piece goes through one mark-only ``effects.Chain`` (what is ready of it is yielded, nothing when that is empty)
     and a last piece carries the flush.  ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``.
-    ``denoise``, ``report``: the input side, forwarded to ``prepare_reference``."""
+    ``denoise``, ``crop``, ``report``: the input side, forwarded to ``prepare_reference``."""
     import dataclasses
 
     from .effects import Chain, Effects
 
     fx = Effects.of(speed, pitch, silence, watermark)
-    segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise, report)
+    segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise, report, crop)
     if not segs:
         return
     mark = Chain.of(Effects(watermark=fx.watermark), tts.device)

@@ -39,11 +39,11 @@ class SoproTTSStreamer:
                ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None,
                nar_context_frames: Optional[int] = None, min_gen_frames: Optional[int] = None,
                text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0,
-               pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None) -> Iterator[torch.Tensor]:
+               pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None) -> Iterator[torch.Tensor]:
         """``speed``, ``pitch``, ``silence``, ``watermark`` (new): every decoded chunk goes through an ``effects.Chain`` and what is
         ready of it is yielded as [1, n] (a step that completes nothing yields nothing); a flush after the last chunk yields the rest.
         The concatenation is ``effects.apply`` of the plain stream's concatenation, bit for bit (``sopro_amd.effects``).
-        ``denoise``, ``report``: the input side, forwarded to ``prepare_reference``."""
+        ``denoise``, ``crop``, ``report``: the input side, forwarded to ``prepare_reference``."""
         from .effects import Chain, Effects
 
         tts = self.tts
@@ -53,7 +53,7 @@ class SoproTTSStreamer:
         ids = text_ids if text_ids is not None else tts.encode_text(text)
         if ref is None:
             ref = tts.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                        report=report)
+                                        report=report, crop=crop)
         prep = model.prepare_conditioning(
             ids, ref, max_frames=max_frames,
             style_strength=float(style_strength if style_strength is not None else tts.cfg.style_strength))
@@ -103,7 +103,7 @@ class SoproTTSStreamer:
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None, nar_context_frames: Optional[int] = None,
                      min_gen_frames: Optional[int] = None, text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                     speed: float = 1.0, pitch: float = 0.0, watermark=None, denoise=None, report: Optional[list] = None):
+                     speed: float = 1.0, pitch: float = 0.0, watermark=None, denoise=None, report: Optional[list] = None, crop=None):
         """``stream`` with word cues (``SoproTTS.stream_timed``): the same sampler draws, chunks and effects chain, and after every
         chunk's decode one step of ``model.AlignStream`` on the frames generated so far.  Yields ``align.TimedChunk``; the words of an
         item are those the step closed, mapped through ``speed`` / ``pitch`` like ``synthesize_timed``'s.  The aligner steps at every
@@ -122,7 +122,7 @@ class SoproTTSStreamer:
             raise ValueError(f"token_spans: {len(spans)} spans for {int(ids.numel())} token ids")
         if ref is None:
             ref = tts.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                        report=report)
+                                        report=report, crop=crop)
         prep = model.prepare_conditioning(
             ids, ref, max_frames=max_frames,
             style_strength=float(style_strength if style_strength is not None else tts.cfg.style_strength))
@@ -181,11 +181,13 @@ def stream_timed(tts, text: str, *, lag_frames: int = 8, token_spans=None, align
     does not exist chunk by chunk), ``lag_frames + chunk_frames > 63`` (the online aligner's window), bad effect values, a bad head
     selection, spans that do not match the text's ids."""
     from . import align as A
+    from .crop import refuse_without_waveform as crop_refuse_without_waveform
     from .denoise import refuse_without_waveform
     from .effects import Effects, refuse
 
     refuse("stream_timed", silence=silence)
     refuse_without_waveform(kwargs.get("denoise"), "stream_timed", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
+    crop_refuse_without_waveform(kwargs.get("crop"), "stream_timed", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
     A.check_align_window(lag_frames, chunk_frames)
     Effects.of(speed, pitch, None, watermark)
     tts.model._align_heads(align_heads)
@@ -201,11 +203,13 @@ def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_t
            pitch: float = 0.0, watermark=None, silence=None, **kwargs) -> Iterator[torch.Tensor]:
     """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch``, ``watermark`` and ``silence`` are new: see
     MimiStreamDecoder, SoproTTSStreamer.stream)"""
+    from .crop import refuse_without_waveform as crop_refuse_without_waveform
     from .denoise import refuse_without_waveform
     from .effects import Effects
 
     Effects.of(speed, pitch, silence, watermark)  # (a bad value is refused here, not at the first chunk)
     refuse_without_waveform(kwargs.get("denoise"), "stream", ref=ref, ref_tokens_tq=ref_tokens_tq)
+    crop_refuse_without_waveform(kwargs.get("crop"), "stream", ref=ref, ref_tokens_tq=ref_tokens_tq)
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
                            chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)

@@ -87,35 +87,41 @@ class SoproTTS:
 
     @torch.inference_mode()
     def encode_speaker(self, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
-                       ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
+                       ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None, crop=None) -> torch.Tensor:
         """reference: src/sopro/model.py:457-475 -> the voice's speaker vector [sv_student_dim] (Token2SV over the cropped
-        reference tokens; the same vector ``prepare_reference`` stores as ``sv_ref``).  ``denoise``, ``report``: as in
+        reference tokens; the same vector ``prepare_reference`` stores as ``sv_ref``).  ``denoise``, ``report``, ``crop``: as in
         ``encode_reference``."""
         ref = self.encode_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                    report=report)
+                                    report=report, crop=crop)
         ref_btq = ref.unsqueeze(0)
         lengths = torch.tensor([int(ref_btq.size(1))], dtype=torch.long)
         return self.model.token2sv(ref_btq, lengths=lengths).squeeze(0).detach()
 
     @torch.inference_mode()
     def encode_reference(self, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
-                         ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
+                         ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None, crop=None) -> torch.Tensor:
         """reference: src/sopro/model.py:477-514 (token path only; audio -> tokens needs the Mimi encoder).  ``denoise`` (new; a
         ``sopro_amd.Denoise``): the reference waveform goes through the stationary-noise suppressor before it is cropped and encoded
         (``MimiCodec.reference_waveform``); ``report``: a list used as a sink, it receives one ``DenoiseReport``.  With
-        ``ref_tokens_tq`` there is no waveform: ``denoise`` other than None is refused."""
+        ``ref_tokens_tq`` there is no waveform: ``denoise`` other than None is refused.  ``crop`` (new; a ``sopro_amd.SpeechCrop``): the
+        ``ref_seconds`` that are encoded are the window with the most speech and the least clipping (``hip.speech_crop``) instead of
+        the centre crop, and ``report`` receives a ``CropReport`` (after the ``DenoiseReport``, if both are asked for); refused with
+        ``ref_tokens_tq`` and with ``ref_seconds <= 0`` (no window to select)."""
+        from . import crop as CR
         from . import denoise as D
 
         D.report_sink(report)
         D.refuse_without_waveform(denoise, "encode_reference", ref_tokens_tq=ref_tokens_tq)
+        CR.refuse_without_waveform(crop, "encode_reference", ref_tokens_tq=ref_tokens_tq)
         if ref_tokens_tq is None and ref_audio_path is None:  # model.py:486-493
             raise RuntimeError("SoproTTS requires a reference. Provide ref_audio_path=... or ref_tokens_tq=...")
         if ref_tokens_tq is not None and ref_audio_path is not None:
             raise RuntimeError("Provide only one of ref_audio_path or ref_tokens_tq (not both).")
         if ref_seconds is None:
             ref_seconds = 12.0  # model.py:495-496
+        CR.refuse_without_window(crop, "encode_reference", ref_seconds)
         if ref_tokens_tq is None:
-            return self.codec.encode_file(ref_audio_path, crop_seconds=ref_seconds if ref_seconds > 0 else None, denoise=denoise, report=report)
+            return self.codec.encode_file(ref_audio_path, crop_seconds=ref_seconds if ref_seconds > 0 else None, denoise=denoise, report=report, crop=crop)
         ref = ref_tokens_tq.long()
         if ref_seconds and ref_seconds > 0:
             fps = float(self.cfg.mimi_fps)
@@ -128,10 +134,10 @@ class SoproTTS:
 
     @torch.inference_mode()
     def prepare_reference(self, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
-                          ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None) -> PreparedReference:
-        """reference: src/sopro/model.py:516-529.  ``denoise``, ``report`` (new): as in ``encode_reference``."""
+                          ref_seconds: Optional[float] = None, denoise=None, report: Optional[list] = None, crop=None) -> PreparedReference:
+        """reference: src/sopro/model.py:516-529.  ``denoise``, ``report``, ``crop`` (new): as in ``encode_reference``."""
         ref = self.encode_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                    report=report)
+                                    report=report, crop=crop)
         return self.model.prepare_reference(ref)
 
     @torch.inference_mode()
@@ -140,22 +146,25 @@ class SoproTTS:
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
                    seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None,
-                   silence=None, denoise=None, report: Optional[list] = None) -> torch.Tensor:
+                   silence=None, denoise=None, report: Optional[list] = None, crop=None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
         draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed``, ``pitch``, ``silence``,
         ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched.
         ``denoise``, ``report`` (new): the input side, forwarded to ``prepare_reference``; with ``ref`` or ``ref_tokens_tq`` there is
-        no waveform to clean and ``denoise`` other than None is refused."""
+        no waveform to clean and ``denoise`` other than None is refused.  ``crop`` (new): which ``ref_seconds`` of the recording are
+        encoded, forwarded likewise and refused likewise."""
+        from . import crop as CR
         from . import denoise as D
         from . import effects
 
         fx = effects.Effects.of(speed, pitch, silence, watermark)
         D.refuse_without_waveform(denoise, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
+        CR.refuse_without_waveform(crop, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
         text_ids = self.encode_text(text)
         if ref is None:
             ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                         report=report)
+                                         report=report, crop=crop)
         tokens = self.model.generate_tokens(
             text_ids, ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
             style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
@@ -291,7 +300,7 @@ class SoproTTS:
                          ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
                          top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                          ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
-                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None):
+                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None):
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
@@ -300,20 +309,22 @@ class SoproTTS:
         ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
         ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12).  ``denoise``,
-        ``report``: as in ``synthesize``."""
+        ``report``, ``crop``: as in ``synthesize``."""
         from . import align as A
+        from . import crop as CR
         from . import denoise as D
         from . import effects
 
         fx = effects.Effects.of(speed, pitch, silence, watermark)
         D.refuse_without_waveform(denoise, "synthesize_timed", ref=ref, ref_tokens_tq=ref_tokens_tq)
+        CR.refuse_without_waveform(crop, "synthesize_timed", ref=ref, ref_tokens_tq=ref_tokens_tq)
         text_ids = self.encode_text(text)
         spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(self.tokenizer, text))
         if len(spans) != int(text_ids.numel()):
             raise ValueError(f"token_spans: {len(spans)} spans for {int(text_ids.numel())} token ids")
         if ref is None:
             ref = self.prepare_reference(ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref_seconds=ref_seconds, denoise=denoise,
-                                         report=report)
+                                         report=report, crop=crop)
         sink: list = []
         tokens = self.model.generate_tokens_batch(
             [text_ids], [ref], max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
@@ -337,7 +348,8 @@ class SoproTTS:
         through the chunked chain of ``sopro_amd.effects`` and what is ready is yielded as [1, n] (with a watermark a chunk comes out
         up to 1440 samples short and the rest follows); the concatenation is ``synthesize``'s chain over the plain stream's
         concatenation, bit for bit (see streaming.SoproTTSStreamer.stream).  ``denoise=``, ``report=`` (keywords of
-        ``prepare_reference``) clean the reference waveform; with ``ref`` or ``ref_tokens_tq`` ``denoise`` is refused here."""
+        ``prepare_reference``) clean the reference waveform, ``crop=`` selects its window; with ``ref`` or ``ref_tokens_tq`` ``denoise``
+        and ``crop`` are refused here."""
         from .align import refuse_timing
         from .streaming import stream
 
@@ -355,8 +367,8 @@ class SoproTTS:
         revises it, so a word is reported about ``lag_frames`` frames after its last frame was generated.  The last item has
         ``final=True``, the remaining words and the ``align.Alignment`` (``status`` 2: the audio ended before the path reached the last
         text position; the words left over get empty cues at the end).  ``token_spans`` / ``align_heads``: as in ``synthesize_timed``.
-        ``silence=`` is refused, and so is ``lag_frames + chunk_frames > 63``; other keywords are ``stream``'s (``denoise=`` and
-        ``report=`` among them)."""
+        ``silence=`` is refused, and so is ``lag_frames + chunk_frames > 63``; other keywords are ``stream``'s (``denoise=``,
+        ``crop=`` and ``report=`` among them)."""
         from .streaming import stream_timed
 
         return stream_timed(self, text, lag_frames=lag_frames, token_spans=token_spans, align_heads=align_heads, speed=speed, pitch=pitch,
@@ -398,7 +410,7 @@ class SoproTTS:
         between sentences are untouched by the squeeze; the pauses are divided by ``speed`` and not touched by ``pitch``.
         ``watermark``: the batches run unmarked and the joined waveform is marked in one launch, so the carrier's phase is continuous
         across the segments (``parts`` stay unmarked).  Full parameter list:
-        ``longform.synthesize_long`` (``denoise=`` and ``report=`` among them: the input side, as in ``synthesize``)."""
+        ``longform.synthesize_long`` (``denoise=``, ``crop=`` and ``report=`` among them: the input side, as in ``synthesize``)."""
         from .longform import synthesize_long
 
         return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
@@ -412,6 +424,7 @@ class SoproTTS:
         and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit.
         ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
         from .align import refuse_timing
+        from .crop import refuse_without_waveform as crop_refuse_without_waveform
         from .denoise import refuse_without_waveform
         from .effects import Effects
         from .longform import stream_long
@@ -419,6 +432,7 @@ class SoproTTS:
         refuse_timing(kwargs, "stream_long")
         Effects.of(speed, pitch, silence, watermark)  # (refused here, not at the first piece)
         refuse_without_waveform(kwargs.get("denoise"), "stream_long", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
+        crop_refuse_without_waveform(kwargs.get("crop"), "stream_long", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
         return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
 
     def detect_watermark(self, wav, key: int):

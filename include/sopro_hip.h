@@ -1237,6 +1237,58 @@ int64_t sopro_crop_workspace_bytes(int32_t rows, int64_t cap);
 int sopro_crop_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens, const float* params, int32_t rows, int32_t win, float* out,
                         int64_t out_stride, int32_t* starts, int32_t* report, void* blocks, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- formant control: a warp of the spectral envelope, length-preserving and without delay -------------------------------- */
+/* No reference counterpart.  Definition (DESIGN.md "Formants"; numpy restatement: tests/formant_ref.py), for one row x of n fp32
+ * samples and one fp32 value inv = 1 / sigma (sigma in [0.5, 2]: the factor the envelope's frequencies are multiplied by), with
+ * N = SOPRO_FM_N, H = SOPRO_FM_H, Q = SOPRO_FM_Q:
+ *   framing    w[i] = sqrt(0.5 (1 - cos(2 pi i / N))) (periodic sqrt-Hann, analysis and synthesis); F = ceil(n / H) + 3 frames;
+ *              xp = x behind N - H zeros, zero-extended to F H + N - H; frame f = xp[f H : f H + N] w; X[f, k] its real DFT,
+ *              k = 0 .. N / 2
+ *   log level  m(k) = 0.5 log(|X(k)|^2 + SOPRO_FM_EPS), extended evenly to N bins: m(N - k) = m(k)
+ *   cepstrum   c_q = (1 / N) sum over the N bins of m(k) cos(2 pi q k / N), q = 0 .. Q - 1; lifter l_q = 0.5 (1 + cos(pi q / Q))
+ *   envelope   L(x) = l_0 c_0 + 2 sum_{q = 1 .. Q - 1} l_q c_q cos(2 pi q x / N) at any real bin position x: evaluated from the
+ *              coefficients, never interpolated between bins
+ *   gain       g(k) = L(min(k inv, N / 2)) - L(k), clamped to +-SOPRO_FM_GAIN_MAX (18 dB in natural-log units); Y(k) = X(k) exp(g(k))
+ *   synthesis  y = 0.5 sum_f w irdft(Y[f]), the four frames on a sample added in ascending f; the output is y[N - H : N - H + n]
+ * At unit gain the row comes back to rounding; an all-zero frame has a flat L and gives zeros.  fp32 throughout: the cepstrum as
+ * m(0) + (-1)^q m(N / 2) + 2 sum_{k = 1 .. N / 2 - 1}, cosines at integer positions from a table of N values made in float64,
+ * cosines at k inv from the exact product k inv = hi + lo split as floor(hi) and a fraction, so the argument handed to cospi is
+ * ((q floor(hi)) mod N + q frac) / (N / 2) and never a large fp32.
+ * One entry point serves the one-shot and the chunked form.
+ * One-shot (state == NULL): wav fp32 [rows] rows row_stride apart (any alignment), out likewise, out_lens[b] = lens[b].
+ * Chunked (state != NULL): state is sopro_formant_state_bytes(rows) bytes of device memory, zero when a row starts: per row two
+ * halves of SOPRO_FM_STATE floats, of which half `phase` holds the last N - H emitted samples (zeros at the start) and the held[b]
+ * samples (0 .. N - 1) that are not emitted yet.  A call appends lens[b] samples; a hop of H samples is emitted once the N samples
+ * of its last frame are in (out_lens[b] = H max((held[b] + lens[b]) / H - 3, 0)), a flush zero-extends and emits everything
+ * (out_lens[b] = held[b] + lens[b]); the call writes the other half of the state (after a flush: zeros), so the caller passes
+ * phase ^ 1 and held[b] + lens[b] - out_lens[b] (after a flush: 0) to the next call.  The frame grid is fixed from the row's
+ * sample 0 and a frame's arithmetic does not depend on the launch it runs in, so the concatenated outputs of any chunking equal the
+ * one-shot row bit for bit.
+ * lens, inv, held (chunked) and out_lens (written before the call returns, may be NULL) are HOST arrays.  inv[b] == 1: the row is
+ * copied bit for bit (chunked: with the same hold-back as the other rows).  Nothing past out_lens[b] of an output row is written.
+ * ws: sopro_formant_workspace_bytes(rows, cap) bytes of device memory for any cap >= max(out_lens), 8-byte aligned (per row and
+ * frame its N synthesised samples; -1: rows <= 0 or cap outside [0, 2^24]).  sopro_formant_chunk_out_cap(n) = n + N: what a chunked
+ * call that appends n samples can emit, rounded up.
+ * Refused (-2, nothing launched): a NULL lens, inv or ws, rows outside 1 .. 65535, a length outside [0, 2^24], an inv outside
+ * [0.5, 2], a held outside 0 .. N - 1, a phase other than 0 or 1, out_lens[b] > out_cap, with rows > 1 a stride below what a row
+ * reads or writes, ws_bytes too small.
+ * Per group of 64 rows two launches on `stream` - frames (one wave per frame, four waves per workgroup: the 256-point complex
+ * radix-4 FFT and the real-input split that denoising uses, the envelope and the gain in LDS, the inverse) and overlap-add (one
+ * workgroup per hop) - and, chunked, one launch that writes the next state.  No float atomics.  The tables are made in float64 on
+ * the host and uploaded on a device's first call; later calls copy nothing, allocate nothing and synchronise nothing. */
+#define SOPRO_FM_N 512
+#define SOPRO_FM_H 128
+#define SOPRO_FM_Q 32
+#define SOPRO_FM_EPS 1e-12f
+#define SOPRO_FM_GAIN_MAX 2.0723265836946410f /* 18 ln(10) / 20 */
+#define SOPRO_FM_STATE 896
+int64_t sopro_formant_workspace_bytes(int32_t rows, int64_t cap);
+int64_t sopro_formant_state_bytes(int32_t rows);
+int64_t sopro_formant_chunk_out_cap(int64_t n);
+int sopro_formant_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens, const float* inv, int32_t rows, void* state,
+                           const int32_t* held, int32_t phase, int32_t flush, float* out, int64_t out_stride, int64_t out_cap,
+                           int32_t* out_lens, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

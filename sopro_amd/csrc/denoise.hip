@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "stft256.h"
 
 namespace {
 
@@ -26,11 +27,16 @@ constexpr int DN_AHEAD = 8;         // frames of one batch of a walk: their oper
 constexpr int FFT_BLOCK = 256, FFT_WAVES = FFT_BLOCK / 64, FFT_FRAMES = 4;  // frames per wave of one workgroup
 constexpr int OLA_BLOCK = H, REP_BLOCK = 256;
 constexpr int64_t LEN_MAX = (int64_t)1 << 24;
-static_assert(N == 512 && H == 128 && NB == N / 2 + 1, "the transform is 256 complex points on 64 lanes, four per lane");
+static_assert(N == stft256::N && H == stft256::H && NB == stft256::NB, "the transform is 256 complex points on 64 lanes, four per lane");
 static_assert(SLOT >= N, "a frame's samples fit where its spectrum was");
 
-// tables: window [512] | exp(-2 pi i m / 256) [256] | exp(-2 pi i k / 512) [257], made in float64 on the host
-constexpr int T_WIN = 0, T_TW = N, T_SPLIT = N + 2 * 256, T_FLOATS = T_SPLIT + 2 * NB;
+// tables: window [512] | exp(-2 pi i m / 256) [256] | exp(-2 pi i k / 512) [257], made in float64 on the host (stft256.h)
+using stft256::cmul;
+using stft256::fft256;
+using stft256::T_FLOATS;
+using stft256::T_SPLIT;
+using stft256::T_TW;
+using stft256::T_WIN;
 __device__ float g_dn_tab[T_FLOATS];
 
 struct Rows {
@@ -55,39 +61,9 @@ __device__ __forceinline__ Ws ws_of(float* ws, int64_t row, int64_t cap) {
   return w;
 }
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
 __device__ __forceinline__ void stage_tables(float* s_tab) {
   for (int i = threadIdx.x; i < T_FLOATS; i += FFT_BLOCK) s_tab[i] = g_dn_tab[i];
   __syncthreads();
-}
-
-// 256-point forward DFT of one wave: lane j enters with points j + 64 t and leaves with outputs j + 64 t (t = 0..3).  Stockham
-// autosort, radix 4: stage Ns in 1, 4, 16, 64 twiddles its inputs by exp(-2 pi i t (j mod Ns) / 4 Ns), does the 4-point DFT and
-// scatters to (j / Ns) 4 Ns + j mod Ns + t Ns; `buf` is the wave's 256 float2 of LDS.
-__device__ __forceinline__ void fft256(float2 (&v)[4], float2* buf, const float2* tw, int j) {
-#pragma unroll
-  for (int ns = 1; ns <= 64; ns <<= 2) {
-    const int k = j & (ns - 1);
-    if (ns > 1) {
-#pragma unroll
-      for (int t = 1; t < 4; ++t) v[t] = cmul(v[t], tw[t * k * (64 / ns)]);
-    }
-    const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y), a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
-    const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y), a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);  // -i (v1 - v3)
-    v[0] = make_float2(a0.x + a2.x, a0.y + a2.y);
-    v[1] = make_float2(a1.x + a3.x, a1.y + a3.y);
-    v[2] = make_float2(a0.x - a2.x, a0.y - a2.y);
-    v[3] = make_float2(a1.x - a3.x, a1.y - a3.y);
-    if (ns == 64) break;  // (j / 64) 256 + j + 64 t: the outputs are where the lane's inputs were
-    const int j0 = ((j & ~(ns - 1)) << 2) + k;
-    wave_lds_sync();  // (the slice's earlier readers are done)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) buf[j0 + t * ns] = v[t];
-    wave_lds_sync();
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[t] = buf[j + 64 * t];
-  }
 }
 
 // ---- analysis ----
@@ -340,10 +316,7 @@ int upload_tables() {
   if (hipGetDevice(&dev) != hipSuccess) return -1;
   if (done[dev & 63]) return 0;
   if (!made) {
-    const double pi = 3.14159265358979323846;
-    for (int i = 0; i < N; ++i) host[T_WIN + i] = (float)sqrt(0.5 * (1.0 - cos(2.0 * pi * i / N)));
-    for (int m = 0; m < 256; ++m) host[T_TW + 2 * m] = (float)cos(2.0 * pi * m / 256), host[T_TW + 2 * m + 1] = (float)-sin(2.0 * pi * m / 256);
-    for (int k = 0; k < NB; ++k) host[T_SPLIT + 2 * k] = (float)cos(2.0 * pi * k / N), host[T_SPLIT + 2 * k + 1] = (float)-sin(2.0 * pi * k / N);
+    stft256::make_tables(host);
     made = true;
   }
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_dn_tab), host, sizeof(host)) != hipSuccess) return -1;

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import gc
 import os
+import struct
 import threading
 from typing import List, Optional, Tuple
 
@@ -294,6 +295,10 @@ SYMBOLS = {
     "sopro_align_online_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
     "sopro_denoise_workspace_bytes": (_i64, [_i32, _i64]),
     "sopro_denoise_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _i64, _p]),
+    "sopro_formant_workspace_bytes": (_i64, [_i32, _i64]),
+    "sopro_formant_state_bytes": (_i64, [_i32]),
+    "sopro_formant_chunk_out_cap": (_i64, [_i64]),
+    "sopro_formant_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i32, _i32, _p, _i64, _i64, _p, _p, _i64, _p]),
     "sopro_crop_workspace_bytes": (_i64, [_i32, _i64]),
     "sopro_crop_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
 }
@@ -1424,6 +1429,109 @@ class PitchShiftState(_RowsState):
         got = _pitch_launch(wav, n, lens_h, self.incs, self.state, flush, out).tolist()
         if min(got) < 0:
             raise SoproHipError("PitchShiftState: a row's outputs did not fit the output buffer")
+        return out[:, : max(got)], got
+
+
+# ---- formant control (sopro_formant_*; definition in include/sopro_hip.h, numpy restatement in tests/formant_ref.py) ----
+FM_N, FM_H, FM_Q, FM_STATE = 512, 128, 32, 896
+FORMANT_ONE = 1.0  # 1 / sigma of a row whose envelope stays where the pitch put it: nothing to do
+formant_calls = 0  # calls of sopro_formant_rows_f32 by this process: the formant=None paths never add to it
+
+
+def formant_inv(formant, pitch=0.0) -> float:
+    """1 / sigma as the fp32 value the device sees (a Python float that holds it exactly), sigma = 2^((formant - pitch) / 12): the
+    factor the envelope is warped by so that it sits ``formant`` semitones from the decoded voice's after a shift by ``pitch``.
+    ``formant=None``: the envelope goes where ``pitch`` takes it, 1.0.  Computed in float64, rounded once.  ``ValueError`` for a
+    ``pitch`` out of range, a ``formant`` that is no finite number, and a sigma outside [0.5, 2]."""
+    pitch_inc(pitch)
+    if formant is None:
+        return FORMANT_ONE
+    try:
+        d = float(formant) - float(pitch)
+    except (TypeError, ValueError):
+        raise ValueError(f"formant must be None or a number of semitones, got {formant!r}") from None
+    if not (-12.0 <= d <= 12.0):  # (NaN fails both comparisons)
+        raise ValueError(f"formant={formant!r} with pitch={pitch!r}: sigma = 2^((formant - pitch) / 12) must lie in [0.5, 2.0]")
+    return struct.unpack("f", struct.pack("f", min(2.0, max(0.5, 2.0 ** (-d / 12.0)))))[0]
+
+
+def _formant_invs_given(invs, rows: int) -> List[float]:
+    vals = [float(v) for v in _per_row(invs, rows, "invs")]
+    if any(not (0.5 <= v <= 2.0) or struct.unpack("f", struct.pack("f", v))[0] != v for v in vals):
+        raise ValueError(f"invs: fp32 values in [0.5, 2.0] (formant_inv), got {vals}")
+    return vals
+
+
+def _formant_launch(wav, lens_h, invs_h, state, held, phase: int, flush: bool, out) -> List[int]:
+    """One sopro_formant_rows_f32 on the current stream -> the rows' output lengths (host arithmetic of the library: no copy)."""
+    global formant_calls
+    rows = len(lens_h)
+    dev = out.device
+    lib = load()
+    n_in = max(lens_h, default=0)
+    with torch.cuda.device(dev):
+        cap = int(out.shape[1])
+        ws_bytes = int(lib.sopro_formant_workspace_bytes(rows, cap))
+        if ws_bytes < 0:
+            raise SoproHipError(f"formant: {rows} rows of up to {cap} samples are outside the operator's range")
+        ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.int64, device=dev)
+        got = (C.c_int32 * rows)()
+        formant_calls += 1
+        _check(lib.sopro_formant_rows_f32(ptr(wav) if n_in > 0 else None, int(wav.stride(0)) if n_in > 0 else 0, (C.c_int32 * rows)(*lens_h),
+                                          (C.c_float * rows)(*invs_h), rows, state.data_ptr() if state is not None else None,
+                                          (C.c_int32 * rows)(*held) if held is not None else None, int(phase), int(bool(flush)), ptr(out),
+                                          int(out.stride(0)), cap, got, ws.data_ptr(), ws_bytes, _stream()), "sopro_formant_rows_f32")
+    return list(got)
+
+
+def formant_shift(wav: torch.Tensor, lens, invs, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The envelope warp of the formant control on the rows of a padded batch (sopro_formant_rows_f32, one-shot form): ``wav`` fp32
+    [rows, >= max(lens)] on the device (rows ``wav.stride(0)`` apart, any alignment), ``lens`` valid samples per row, ``invs`` one
+    1 / sigma or one per row (``formant_inv``) -> out [rows, max(lens)], row b valid for lens[b] samples: the row with its spectral
+    envelope's frequencies multiplied by sigma, its pitch, length and timing as they were; a row at 1.0 comes back bit for bit.  Two
+    launches per 64 rows on the current stream and no synchronisation.  ``out``: a [rows, >= max(lens)] fp32 buffer to write into
+    (nothing past a row's length is touched); it must not overlap ``wav``.  All rows at 1.0: nothing is launched and
+    ``wav[:, :max(lens)]`` is returned as it is."""
+    lens_h = _lens_list(lens)
+    rows = len(lens_h)
+    _check_rows(wav, lens_h, "formant_shift")
+    invs_h = _formant_invs_given(invs, rows)
+    cap = max(lens_h, default=0)
+    _out_buffer(out, rows, cap, "formant_shift")
+    if rows == 0 or cap == 0 or all(v == FORMANT_ONE for v in invs_h):
+        if out is None:
+            return wav[:, :cap]
+        out[:, :cap].copy_(wav[:, :cap])  # (a caller that asked for its own buffer gets the rows there)
+        return out[:, :cap]
+    if out is None:
+        out = torch.empty(rows, cap, dtype=torch.float32, device=wav.device)
+    _formant_launch(wav, lens_h, invs_h, None, None, 0, True, out)
+    return out[:, :cap]
+
+
+class FormantState(_RowsState):
+    """Chunked form of ``formant_shift`` for ``rows`` streams: ``feed`` appends a chunk per row and returns the 128-sample hops whose
+    four frames are all in (a hop comes out once the 512 samples of its last frame are there, so fewer than 512 samples are held
+    back), ``flush`` the rest, zero-extended.  Any chunking followed by ``flush`` gives the one-shot result bit for bit: the frame
+    grid is fixed from sample 0.  The state (the last 384 emitted samples and the held ones, two halves written in turn) lives on the
+    device; the counts are host arithmetic, so a call is two or three launches and copies nothing back."""
+
+    _op = "formant"
+
+    def __init__(self, rows: int, invs, device):
+        super().__init__(rows, device)
+        self.invs = _formant_invs_given(invs, self.rows)
+        self.held = [0] * self.rows
+        self.phase = 0
+
+    def feed(self, wav: Optional[torch.Tensor], lens=None, *, flush: bool = False):
+        """``wav`` [rows, n] (row b valid for lens[b] samples; default n) -> (out [rows, max(out_lens)], out_lens)."""
+        n, lens_h, out = self._chunk(wav, lens)
+        if n == 0 and not (flush and any(self.held)):  # (nothing new and nothing to bring out: the state stays as it is)
+            return out[:, :0], [0] * self.rows
+        got = _formant_launch(wav, lens_h, self.invs, self.state, self.held, self.phase, flush, out)
+        self.held = [0 if flush else h + a - g for h, a, g in zip(self.held, lens_h, got)]
+        self.phase ^= 1
         return out[:, : max(got)], got
 
 

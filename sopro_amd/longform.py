@@ -227,14 +227,15 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
                     keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None,
-                    pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None) -> LongformResult:
+                    pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None,
+                    formant: Optional[float] = None) -> LongformResult:
     """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
     (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k, after ``effects.map_cues`` has
     taken it through its row's rate, pitch and cut table).  ``token_spans``: a callable text -> [(start, end)] per token id for
     tokenizers that give no character offsets; ``align_heads``: the (layer, head) pairs to average.  ``watermark``: the batches get no
     mark (parts stay unmarked); the joined waveform is marked in one launch, so the carrier's phase runs on across the segments and no
-    cue moves.  ``denoise``, ``crop``, ``report``: the input side, forwarded to ``prepare_reference`` (refused with ``ref`` or ``ref_tokens_tq``)."""
+    cue moves.  ``formant``: every row is warped in its batch, like ``pitch``.  ``denoise``, ``crop``, ``report``: the input side, forwarded to ``prepare_reference`` (refused with ``ref`` or ``ref_tokens_tq``)."""
     import dataclasses
 
     import torch
@@ -242,7 +243,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     from . import align as A
     from . import effects
 
-    fx = effects.Effects.of(speed, pitch, silence, watermark)  # (a bad value is refused before anything runs)
+    fx = effects.Effects.of(speed, pitch, silence, watermark, formant)  # (a bad value is refused before anything runs)
     rows = dataclasses.replace(fx, watermark=None)
     if token_spans is not None and not callable(token_spans):
         raise TypeError("synthesize_long(token_spans=...) wants a callable: segment text -> [(start, end)] per token id")
@@ -283,7 +284,8 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
                 style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
                 max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0, keep_ms: float = 30.0,
                 fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "latency", max_rows: int = 32, speed: float = 1.0,
-                pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None) -> Iterator[Any]:
+                pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None,
+                formant: Optional[float] = None) -> Iterator[Any]:
     """The same text as a generator of joined pieces, one [1, n] tensor per group of the plan (see ``SoproTTS.stream_long``).
     ``watermark``: every piece goes through one mark-only ``effects.Chain`` (what is ready of it is yielded, nothing when that is empty)
     and a last piece carries the flush.  ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``.
@@ -292,7 +294,7 @@ def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = Non
 
     from .effects import Chain, Effects
 
-    fx = Effects.of(speed, pitch, silence, watermark)
+    fx = Effects.of(speed, pitch, silence, watermark, formant)
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise, report, crop)
     if not segs:
         return

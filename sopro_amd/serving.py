@@ -32,7 +32,7 @@ class _Request:
     t_submit: float
     stream: Optional["_StreamSink"] = None  # submit_stream: where the lane puts this row's chunks
     seed: Optional[int] = None
-    fx: Any = None  # submit: this request's effects.Effects - applied after decoding, one per row, so no part of the batching key
+    fx: Any = None  # submit: this request's effects.Effects (formant included) - applied after decoding, one per row, so no part of the batching key
     silence: Any = None  # the silence control of this request: applied after rate and pitch, one per row
 
 
@@ -119,9 +119,9 @@ class SynthesisService:
     def submit(self, text: str, ref: PreparedReference, *, max_frames: int = 400, top_p: float = 0.9, temperature: float = 1.05,
                anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                text_ids: Optional[torch.Tensor] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
-               **timing) -> "Future[torch.Tensor]":
+               formant: Optional[float] = None, **timing) -> "Future[torch.Tensor]":
         """Queue one utterance; the future resolves to the waveform ``[1, 1, N]`` on the device (``synthesize``'s result).
-        ``speed``, ``pitch``, ``silence``, ``watermark`` (``sopro_amd.effects``; ``mode="batch"`` only): this request's own.  They are
+        ``speed``, ``pitch``, ``formant``, ``silence``, ``watermark`` (``sopro_amd.effects``; ``mode="batch"`` only): this request's own.  They are
         applied to the decoded batch, one setting per row, so requests (and tenants) that differ in them share a batch.  The service
         has no word timing in either mode: a timing keyword (``alignment``, ``word_cues``, ...) raises."""
         from . import effects
@@ -132,9 +132,9 @@ class SynthesisService:
             raise TypeError(f"submit() got unexpected keyword arguments {sorted(timing)}")
         if self._closed:
             raise RuntimeError("service is closed")
-        fx = effects.Effects.of(speed, pitch, silence, watermark)
+        fx = effects.Effects.of(speed, pitch, silence, watermark, formant)
         if self.engine is not None:
-            effects.refuse("SynthesisService(mode='continuous')", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
+            effects.refuse("SynthesisService(mode='continuous')", speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant)
             self.stats["requests"] += 1
             return self.engine.submit(text=text, text_ids=text_ids, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature,
                                       anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames)
@@ -151,17 +151,18 @@ class SynthesisService:
                       anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                       text_ids: Optional[torch.Tensor] = None, chunk_frames: int = 6, cache_trim: str = "none",
                       nar_context_frames: Optional[int] = None, seed: Optional[int] = None, speed: float = 1.0,
-                      pitch: float = 0.0, watermark=None, silence=None) -> Iterator[torch.Tensor]:
+                      pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None) -> Iterator[torch.Tensor]:
         """Queue one streamed utterance -> a blocking iterator over its [1, n * 1920] chunks (``stream``'s chunks).  Streams with equal
         parameters are grouped into batches of up to ``max_batch`` rows (within ``max_wait_ms``) and each batch runs as one
         ``stream_batch`` on a lane, sharing the device with whole-utterance batches (AR lock per chunk, bulk lock for refinement and
-        decoding).  Closing or dropping the iterator drops the row from its batch.  Batched streams have none of the four effects:
-        ``speed`` other than 1.0, ``pitch`` other than 0.0, ``watermark`` or ``silence`` other than None raises."""
+        decoding).  Closing or dropping the iterator drops the row from its batch.  Batched streams have none of the five effects:
+        ``speed`` other than 1.0, ``pitch`` other than 0.0, a ``formant`` other than None or ``pitch``, ``watermark`` or ``silence`` other than
+        None raises."""
         from .effects import refuse
 
         if self._closed:
             raise RuntimeError("service is closed")
-        refuse("submit_stream", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
+        refuse("submit_stream", speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant)
         if self.engine is not None:
             raise RuntimeError("submit_stream is not available in mode='continuous' (frame-level admission has no streaming path); "
                                "use mode='batch'")
@@ -181,18 +182,18 @@ class SynthesisService:
                     anti_loop: bool = True, style_strength: Optional[float] = None, min_gen_frames: Optional[int] = None,
                     max_chars: int = 280, pauses_ms: Optional[Dict[str, float]] = None, trim_db: Optional[float] = -40.0,
                     keep_ms: float = 30.0, fade_ms: float = 5.0, keep_parts: bool = False, speed: float = 1.0,
-                    pitch: float = 0.0, watermark=None, silence=None) -> "Future":
+                    pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None) -> "Future":
         """Queue a text of any length -> a future of ``longform.LongformResult`` (``SoproTTS.synthesize_long``'s result).  The text is
         split here and every segment goes through ``submit``, so the scheduler batches the segments with whatever else is queued;
         a small waiter thread gathers the segment futures in order, stacks them into one padded tensor and joins them on the
         device (``hip.join_segments``).  The sampler draws as ``submit`` draws (a fresh take per segment: no seed, no group plan).
-        ``speed``, ``pitch``, ``silence``: every segment is submitted with them (applied in its batch, before the join); the pauses are
+        ``speed``, ``pitch``, ``formant``, ``silence``: every segment is submitted with them (applied in its batch, before the join); the pauses are
         divided by ``speed`` only.  ``watermark``: the segments are submitted unmarked and the joined waveform is marked, as in
         ``SoproTTS.synthesize_long``."""
         from . import effects, hip
         from .longform import LongformPart, LongformResult, join_params, pause_samples, scaled_pause, split_text
 
-        fx = effects.Effects.of(speed, pitch, silence, watermark)
+        fx = effects.Effects.of(speed, pitch, silence, watermark, formant)
         mark = effects.Effects(watermark=fx.watermark)
 
         if self._closed:
@@ -203,7 +204,8 @@ class SynthesisService:
         gaps = [scaled_pause(pause_samples(s.boundary, pauses_ms), speed) for s in segs]
         join_kw = join_params(trim_db, keep_ms, fade_ms)
         futs = [self.submit(s.text, ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
-                            style_strength=style_strength, min_gen_frames=min_gen_frames, speed=speed, pitch=pitch, silence=silence) for s in segs]
+                            style_strength=style_strength, min_gen_frames=min_gen_frames, speed=speed, pitch=pitch, silence=silence,
+                            formant=formant) for s in segs]
         done: Future = Future()
         dev = self.tts.device
 

@@ -39,15 +39,16 @@ class SoproTTSStreamer:
                ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None,
                nar_context_frames: Optional[int] = None, min_gen_frames: Optional[int] = None,
                text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None, speed: float = 1.0,
-               pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None) -> Iterator[torch.Tensor]:
-        """``speed``, ``pitch``, ``silence``, ``watermark`` (new): every decoded chunk goes through an ``effects.Chain`` and what is
+               pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None,
+               formant: Optional[float] = None) -> Iterator[torch.Tensor]:
+        """``speed``, ``pitch``, ``formant``, ``silence``, ``watermark`` (new): every decoded chunk goes through an ``effects.Chain`` and what is
         ready of it is yielded as [1, n] (a step that completes nothing yields nothing); a flush after the last chunk yields the rest.
         The concatenation is ``effects.apply`` of the plain stream's concatenation, bit for bit (``sopro_amd.effects``).
         ``denoise``, ``crop``, ``report``: the input side, forwarded to ``prepare_reference``."""
         from .effects import Chain, Effects
 
         tts = self.tts
-        chain = Chain.of(Effects.of(speed, pitch, silence, watermark), tts.device)
+        chain = Chain.of(Effects.of(speed, pitch, silence, watermark, formant), tts.device)
 
         model = tts.model
         ids = text_ids if text_ids is not None else tts.encode_text(text)
@@ -103,7 +104,8 @@ class SoproTTSStreamer:
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      ref_seconds: Optional[float] = None, chunk_frames: Optional[int] = None, nar_context_frames: Optional[int] = None,
                      min_gen_frames: Optional[int] = None, text_ids: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                     speed: float = 1.0, pitch: float = 0.0, watermark=None, denoise=None, report: Optional[list] = None, crop=None):
+                     speed: float = 1.0, pitch: float = 0.0, watermark=None, denoise=None, report: Optional[list] = None, crop=None,
+                     formant: Optional[float] = None):
         """``stream`` with word cues (``SoproTTS.stream_timed``): the same sampler draws, chunks and effects chain, and after every
         chunk's decode one step of ``model.AlignStream`` on the frames generated so far.  Yields ``align.TimedChunk``; the words of an
         item are those the step closed, mapped through ``speed`` / ``pitch`` like ``synthesize_timed``'s.  The aligner steps at every
@@ -114,7 +116,7 @@ class SoproTTSStreamer:
         from .effects import Chain, Effects, map_cues
 
         tts = self.tts
-        fx = Effects.of(speed, pitch, None, watermark)
+        fx = Effects.of(speed, pitch, None, watermark, formant)
         chain = Chain.of(fx, tts.device)
         model = tts.model
         ids = text_ids if text_ids is not None else tts.encode_text(text)
@@ -175,7 +177,7 @@ class SoproTTSStreamer:
 
 @torch.inference_mode()
 def stream_timed(tts, text: str, *, lag_frames: int = 8, token_spans=None, align_heads=None, chunk_frames: int = 6, cache_trim: str = "none",
-                 speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, **kwargs):
+                 speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None, **kwargs):
     """New: ``stream`` with word cues as they are committed -> an iterator of ``align.TimedChunk`` (see
     SoproTTSStreamer.stream_timed).  Everything that can be refused is refused here, before anything runs: ``silence=`` (its cut table
     does not exist chunk by chunk), ``lag_frames + chunk_frames > 63`` (the online aligner's window), bad effect values, a bad head
@@ -189,30 +191,30 @@ def stream_timed(tts, text: str, *, lag_frames: int = 8, token_spans=None, align
     refuse_without_waveform(kwargs.get("denoise"), "stream_timed", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
     crop_refuse_without_waveform(kwargs.get("crop"), "stream_timed", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
     A.check_align_window(lag_frames, chunk_frames)
-    Effects.of(speed, pitch, None, watermark)
+    Effects.of(speed, pitch, None, watermark, formant)
     tts.model._align_heads(align_heads)
     spans = token_spans(text) if callable(token_spans) else (list(token_spans) if token_spans is not None else A.token_spans(tts.tokenizer, text))
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream_timed(text, spans, lag_frames=lag_frames, align_heads=align_heads, chunk_frames=chunk_frames, speed=speed,
-                                 pitch=pitch, watermark=watermark, **kwargs)
+                                 pitch=pitch, watermark=watermark, formant=formant, **kwargs)
 
 
 @torch.inference_mode()
 def stream(tts, text: str, *, ref_audio_path: Optional[str] = None, ref_tokens_tq: Optional[torch.Tensor] = None,
            ref: Optional[PreparedReference] = None, chunk_frames: int = 6, cache_trim: str = "none", speed: float = 1.0,
-           pitch: float = 0.0, watermark=None, silence=None, **kwargs) -> Iterator[torch.Tensor]:
-    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch``, ``watermark`` and ``silence`` are new: see
+           pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None, **kwargs) -> Iterator[torch.Tensor]:
+    """reference: src/sopro/streaming.py:133-152 (``cache_trim``, ``speed``, ``pitch``, ``formant``, ``watermark`` and ``silence`` are new: see
     MimiStreamDecoder, SoproTTSStreamer.stream)"""
     from .crop import refuse_without_waveform as crop_refuse_without_waveform
     from .denoise import refuse_without_waveform
     from .effects import Effects
 
-    Effects.of(speed, pitch, silence, watermark)  # (a bad value is refused here, not at the first chunk)
+    Effects.of(speed, pitch, silence, watermark, formant)  # (a bad value is refused here, not at the first chunk)
     refuse_without_waveform(kwargs.get("denoise"), "stream", ref=ref, ref_tokens_tq=ref_tokens_tq)
     crop_refuse_without_waveform(kwargs.get("crop"), "stream", ref=ref, ref_tokens_tq=ref_tokens_tq)
     streamer = SoproTTSStreamer(tts, StreamConfig(chunk_frames=chunk_frames, cache_trim=cache_trim))
     return streamer.stream(text, ref_audio_path=ref_audio_path, ref_tokens_tq=ref_tokens_tq, ref=ref,
-                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
+                           chunk_frames=chunk_frames, speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant, **kwargs)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -267,17 +269,17 @@ def stream_batch(tts, texts: Sequence[str], refs: Sequence, *, chunk_frames: int
                  nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
                  phase_locks: Optional[tuple] = None, timings: Optional[Dict[str, float]] = None,
                  alive: Optional[Callable[[int], bool]] = None, speed: float = 1.0,
-                 pitch: float = 0.0, watermark=None, silence=None) -> Iterator[List[Optional[torch.Tensor]]]:
+                 pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None) -> Iterator[List[Optional[torch.Tensor]]]:
     """B utterances streamed in lockstep.  Yields, per step, a list of B entries: a [1, n * 1920] chunk or None.  Row b's non-None
     chunks are what ``stream(texts[b], ref=refs[b], seed=seeds[b], ...)`` yields: same chunk sizes, same stop rule (first EOS).
     ``seeds``: one per row (None: a fresh take for that row).  ``phase_locks`` = (AR lock, bulk lock): held around the AR advance and
     around refinement + decode of every step (a serving lane shares its device with whole-utterance batches).  ``timings``: seconds
     of host wall time accumulated under "ar", "refine", "decode".  ``alive(b)`` (a server): False once row b's consumer has gone - the
     row then leaves the batch at the next step as if it had ended there.  ``speed``: only 1.0, ``pitch``: only 0.0,
-    ``watermark``, ``silence``: only None (batched streams have none of the four effects)."""
+    ``formant``: only None or ``pitch``, ``watermark``, ``silence``: only None (batched streams have none of the five effects)."""
     from .effects import refuse
 
-    refuse("stream_batch", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
+    refuse("stream_batch", speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant)
     model = tts.model
     B = len(texts)
     if B == 0 or len(refs) != B:

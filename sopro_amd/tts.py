@@ -146,11 +146,11 @@ class SoproTTS:
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
                    seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None,
-                   silence=None, denoise=None, report: Optional[list] = None, crop=None) -> torch.Tensor:
+                   silence=None, denoise=None, report: Optional[list] = None, crop=None, formant: Optional[float] = None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
-        draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed``, ``pitch``, ``silence``,
-        ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched.
+        draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed``, ``pitch``, ``formant``,
+        ``silence``, ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched.
         ``denoise``, ``report`` (new): the input side, forwarded to ``prepare_reference``; with ``ref`` or ``ref_tokens_tq`` there is
         no waveform to clean and ``denoise`` other than None is refused.  ``crop`` (new): which ``ref_seconds`` of the recording are
         encoded, forwarded likewise and refused likewise."""
@@ -158,7 +158,7 @@ class SoproTTS:
         from . import denoise as D
         from . import effects
 
-        fx = effects.Effects.of(speed, pitch, silence, watermark)
+        fx = effects.Effects.of(speed, pitch, silence, watermark, formant)
         D.refuse_without_waveform(denoise, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
         CR.refuse_without_waveform(crop, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
         text_ids = self.encode_text(text)
@@ -183,13 +183,13 @@ class SoproTTS:
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
                          speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
                          align_heads=None, pitch: Union[float, Sequence[float]] = 0.0,
-                         watermark=None, silence=None, effects=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         watermark=None, silence=None, effects=None, formant=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
         ``PaddedBatch`` of ``wav`` [B, T * 1920], ``lens`` (valid samples per row) and ``tokens`` [B, T, Q] (a copy: the engine's
         own token matrix is overwritten by the next pass); the list above is ``[wav[b, :lens[b]].reshape(1, 1, -1)]``.
-        ``speed``, ``pitch``, ``silence``, ``watermark``: one value or one per row each (None entries allowed in the last two), see
+        ``speed``, ``pitch``, ``formant``, ``silence``, ``watermark``: one value or one per row each (None entries allowed in the last three), see
         ``sopro_amd.effects``; the decoder's padded batch goes through the chain on the bulk stream before it is sliced, so
         ``PaddedBatch.wav`` / ``lens`` are the finished rows and ``cuts`` their cut tables (None without ``silence``), while ``tokens``
         and ``frames`` stay what the model produced.
@@ -197,7 +197,7 @@ class SoproTTS:
         position path, frame range per position, confidence; in frames, before any stretch) by a post-pass on the bulk stream
         (``model.align_batch``: the AR stack replayed over the generated tokens, ``hip.align_scores`` / ``hip.align_paths``);
         ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched.
-        ``effects`` (internal): the rows' ``effects.Effects`` as they are, instead of the four keywords."""
+        ``effects`` (internal): the rows' ``effects.Effects`` as they are, instead of the five keywords."""
         import contextlib
         import time
 
@@ -205,7 +205,7 @@ class SoproTTS:
 
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
         # (a bad value is refused before anything runs)
-        fxs = list(effects) if effects is not None else E.per_row(speed, pitch, silence, watermark, len(ids))
+        fxs = list(effects) if effects is not None else E.per_row(speed, pitch, silence, watermark, len(ids), formant)
         if len(fxs) != len(ids):
             raise ValueError(f"effects: one per row ({len(ids)}), got {len(fxs)}")
         if alignment is not None:
@@ -300,12 +300,13 @@ class SoproTTS:
                          ref_tokens_tq: Optional[torch.Tensor] = None, token_spans=None, align_heads=None, max_frames: int = 400,
                          top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                          ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None, seed: Optional[int] = None,
-                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None):
+                         speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None,
+                         formant: Optional[float] = None):
         """New: ``synthesize`` with word timestamps -> ``align.TimedResult(wav, words, alignment)``.  ``wav`` is what ``synthesize``
         returns for the same arguments (same sampler stream, same launches: bit-identical for the same ``seed``); ``words`` holds one
         ``align.WordCue`` (text, character range, sample range in ``wav``) per whitespace-separated word; ``alignment`` the frame-level
         ``align.Alignment`` with its ``confidence``.  Cues are whole frames (1920 samples) and follow the audio through ``speed``,
-        ``pitch`` and ``silence`` (``effects.map_cues`` has their accuracy); the mark changes no length, so it moves no cue.
+        ``pitch`` and ``silence`` (``effects.map_cues`` has their accuracy); ``formant`` and the mark move no sample, so they move no cue.
         ``token_spans``: the character span
         of every id of ``encode_text(text)`` (a list, or a callable text -> list) for tokenizers without character offsets;
         ``align_heads``: the (layer, head) pairs to average, picked with tools/align_probe.py (default all 12).  ``denoise``,
@@ -315,7 +316,7 @@ class SoproTTS:
         from . import denoise as D
         from . import effects
 
-        fx = effects.Effects.of(speed, pitch, silence, watermark)
+        fx = effects.Effects.of(speed, pitch, silence, watermark, formant)
         D.refuse_without_waveform(denoise, "synthesize_timed", ref=ref, ref_tokens_tq=ref_tokens_tq)
         CR.refuse_without_waveform(crop, "synthesize_timed", ref=ref, ref_tokens_tq=ref_tokens_tq)
         text_ids = self.encode_text(text)
@@ -342,9 +343,9 @@ class SoproTTS:
         """Another engine over the same device weights (own streams / scratch), for pipelining batches."""
         return SoproTTS(self.model.clone_lane(), self.cfg, self.tokenizer, self.codec.clone_lane(), str(self.device))
 
-    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+    def stream(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None,
                **kwargs) -> Iterator[torch.Tensor]:
-        """reference: src/sopro/model.py:577-580.  ``speed``, ``pitch``, ``silence``, ``watermark`` (new): every decoded chunk goes
+        """reference: src/sopro/model.py:577-580.  ``speed``, ``pitch``, ``formant``, ``silence``, ``watermark`` (new): every decoded chunk goes
         through the chunked chain of ``sopro_amd.effects`` and what is ready is yielded as [1, n] (with a watermark a chunk comes out
         up to 1440 samples short and the rest follows); the concatenation is ``synthesize``'s chain over the plain stream's
         concatenation, bit for bit (see streaming.SoproTTSStreamer.stream).  ``denoise=``, ``report=`` (keywords of
@@ -354,15 +355,15 @@ class SoproTTS:
         from .streaming import stream
 
         refuse_timing(kwargs, "stream")
-        return stream(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
+        return stream(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant, **kwargs)
 
     def stream_timed(self, text: str, *, lag_frames: int = 8, token_spans=None, align_heads=None, speed: float = 1.0, pitch: float = 0.0,
-                     watermark=None, silence=None, chunk_frames: int = 6, **kwargs):
+                     watermark=None, silence=None, chunk_frames: int = 6, formant: Optional[float] = None, **kwargs):
         """New: ``stream`` with word timestamps as the audio is generated -> an iterator of ``align.TimedChunk(wav, words, final,
         alignment)``.  The ``wav`` fields ([1, n], n may be 0) concatenate to what ``stream`` yields for the same arguments and
         ``seed``, bit for bit; ``words`` holds an ``align.WordCue`` for every word the step closed, in text order, samples on the
-        timeline of the concatenated output (through ``speed`` and ``pitch`` with ``synthesize_timed``'s accuracy; the mark moves no
-        cue).  A cue is final when it is yielded: the online aligner (``hip.align_online``) commits a frame once ``lag_frames``
+        timeline of the concatenated output (through ``speed`` and ``pitch`` with ``synthesize_timed``'s accuracy; ``formant`` and the
+        mark move no cue).  A cue is final when it is yielded: the online aligner (``hip.align_online``) commits a frame once ``lag_frames``
         later frames are in (default 8, 640 ms: a guess until a trained checkpoint is probed with tools/align_probe.py) and never
         revises it, so a word is reported about ``lag_frames`` frames after its last frame was generated.  The last item has
         ``final=True``, the remaining words and the ``align.Alignment`` (``status`` 2: the audio ended before the path reached the last
@@ -372,30 +373,31 @@ class SoproTTS:
         from .streaming import stream_timed
 
         return stream_timed(self, text, lag_frames=lag_frames, token_spans=token_spans, align_heads=align_heads, speed=speed, pitch=pitch,
-                            watermark=watermark, silence=silence, chunk_frames=chunk_frames, **kwargs)
+                            watermark=watermark, silence=silence, chunk_frames=chunk_frames, formant=formant, **kwargs)
 
     def stream_batch(self, texts: Sequence[str], refs: Sequence[PreparedReference], *, chunk_frames: int = 6, max_frames: int = 400,
                      top_p: float = 0.9, temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                      min_gen_frames: Optional[int] = None, seeds: Optional[Sequence[Optional[int]]] = None, cache_trim: str = "none",
                      nar_context_frames: Optional[int] = None, text_ids: Optional[Sequence[torch.Tensor]] = None,
-                     speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+                     speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None,
                      **kwargs) -> Iterator[List[Optional[torch.Tensor]]]:
         """New: B streams in lockstep (one batched AR run, refinement and stream decode per chunk).  Yields per step a list of B
         entries, a [1, n * 1920] chunk or None; row b's chunks are what ``stream`` yields for it (see streaming.stream_batch).
-        None of the four effects is available here (``speed`` other than 1.0, ``pitch`` other than 0.0, ``watermark`` or ``silence``
-        other than None raises): use ``stream`` or ``synthesize_batch``."""
+        None of the five effects is available here (``speed`` other than 1.0, ``pitch`` other than 0.0, a ``formant`` other than None
+        or ``pitch``, ``watermark`` or ``silence`` other than None raises): use ``stream`` or ``synthesize_batch``."""
         from . import effects
         from .align import refuse_timing
         from .streaming import stream_batch
 
         refuse_timing(kwargs, "stream_batch")
-        effects.refuse("stream_batch", speed=speed, pitch=pitch, watermark=watermark, silence=silence)
+        effects.refuse("stream_batch", speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant)
         return stream_batch(self, texts, refs, chunk_frames=chunk_frames, max_frames=max_frames, top_p=top_p, temperature=temperature,
                             anti_loop=anti_loop, style_strength=style_strength, min_gen_frames=min_gen_frames, seeds=seeds,
                             cache_trim=cache_trim, nar_context_frames=nar_context_frames, text_ids=text_ids, speed=speed, pitch=pitch,
                             **kwargs)
 
-    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, **kwargs):
+    def synthesize_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+                        formant: Optional[float] = None, **kwargs):
         """New: a text of any length (a paragraph, an article, a chapter) -> ``LongformResult``: ``wav`` [1, 1, N] on the device and
         ``segments`` [(text, start sample, end sample)] in it.  The text is cut into sentences (``longform.split_text``,
         ``max_chars``), the voice is prepared once, groups of up to ``max_rows`` segments (``plan``: "throughput", "latency" or a
@@ -405,7 +407,7 @@ class SoproTTS:
         fades.  ``max_frames`` and the sampling parameters are per segment, as in ``synthesize``; segment k draws as
         ``synthesize(segment_k, ref=ref, seed=seed + k)`` does.  ``keep_parts=True`` also returns every segment's untrimmed
         waveform and tokens (``parts``) and the kept range (``edges``).  ``word_cues=True`` also fills ``words`` (one
-        ``align.LongWordCue`` per word, samples in the joined waveform).  ``speed``, ``pitch``, ``silence`` (``sopro_amd.effects``): every group's padded batch goes through them
+        ``align.LongWordCue`` per word, samples in the joined waveform).  ``speed``, ``pitch``, ``formant``, ``silence`` (``sopro_amd.effects``): every group's padded batch goes through them
         before the join, so ``parts`` are the finished rows, cue times refer to the audio as it is heard and the pauses the join puts
         between sentences are untouched by the squeeze; the pauses are divided by ``speed`` and not touched by ``pitch``.
         ``watermark``: the batches run unmarked and the joined waveform is marked in one launch, so the carrier's phase is continuous
@@ -413,13 +415,14 @@ class SoproTTS:
         ``longform.synthesize_long`` (``denoise=``, ``crop=`` and ``report=`` among them: the input side, as in ``synthesize``)."""
         from .longform import synthesize_long
 
-        return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
+        return synthesize_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant, **kwargs)
 
-    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None,
+    def stream_long(self, text: str, *, speed: float = 1.0, pitch: float = 0.0, watermark=None, silence=None, formant: Optional[float] = None,
                     **kwargs) -> Iterator[torch.Tensor]:
         """New: ``synthesize_long`` as a generator: runs group g of the plan ("latency" by default: 1, 2, 4, ... segments), joins it,
         yields the joined piece [1, n] (its trailing pause included), then runs group g + 1.  The join has no overlap between
-        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed`` and ``pitch``).
+        segments, so the pieces concatenate to ``synthesize_long(..., plan="latency").wav`` bit for bit (at any ``speed``, ``pitch`` and
+        ``formant``).
         ``watermark``: the pieces go through one chunked mark (a piece comes out up to 1440 samples short, the rest follows,
         and a last piece carries the flush); they concatenate to ``synthesize_long(..., plan="latency", watermark=...).wav`` bit for bit.
         ``silence``: every group's batch is squeezed before its join, as in ``synthesize_long``."""
@@ -430,10 +433,10 @@ class SoproTTS:
         from .longform import stream_long
 
         refuse_timing(kwargs, "stream_long")
-        Effects.of(speed, pitch, silence, watermark)  # (refused here, not at the first piece)
+        Effects.of(speed, pitch, silence, watermark, formant)  # (refused here, not at the first piece)
         refuse_without_waveform(kwargs.get("denoise"), "stream_long", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
         crop_refuse_without_waveform(kwargs.get("crop"), "stream_long", ref=kwargs.get("ref"), ref_tokens_tq=kwargs.get("ref_tokens_tq"))
-        return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, **kwargs)
+        return stream_long(self, text, speed=speed, pitch=pitch, watermark=watermark, silence=silence, formant=formant, **kwargs)
 
     def detect_watermark(self, wav, key: int):
         """New: does ``wav`` carry the mark of ``key``?  -> ``watermark.WatermarkResult(present, score, tag, offset, z_sync, z_tag)``,

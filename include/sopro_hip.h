@@ -1289,6 +1289,69 @@ int sopro_formant_rows_f32(const float* wav, int64_t row_stride, const int32_t* 
                            const int32_t* held, int32_t phase, int32_t flush, float* out, int64_t out_stride, int64_t out_cap,
                            int32_t* out_lens, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- pitch tracking: the fundamental frequency of every 10 ms frame of a waveform ------------------------------------------- */
+/* No reference counterpart.  An analysis: it reads a waveform and changes none.  Definition (DESIGN.md "Pitch tracking"; numpy
+ * restatement: tests/f0_ref.py), for one row x of n fp32 samples at the codec rate (24 kHz), with H = SOPRO_F0_H, W = SOPRO_F0_W = 3 H,
+ * TMIN = SOPRO_F0_TMIN (500 Hz), TMAX = SOPRO_F0_TMAX (60 Hz), SPAN = W + TMAX, K = SOPRO_F0_K:
+ *   frames     F = 0 for n < SPAN, else (n - SPAN) / H + 1; frame f reads x[f H : f H + SPAN) and nothing else; it describes the
+ *              sample f H + SPAN / 2
+ *   difference d[f][t] = sum_{j < W} (x[f H + j] - x[f H + j + t])^2 for t = 1 .. TMAX; e[f] = sum_{j < W} x[f H + j]^2
+ *   normalise  c[f][t] = d[f][1] + .. + d[f][t]; v[f][t] = d[f][t] t / c[f][t], or 1 where c is 0 (YIN's cumulative-mean-normalised
+ *              difference); v[f][0] = 1 and is never used
+ *   candidates only if e[f] > gate = W 10^(floor_db / 10) (computed in double from the fp32 floor_db, rounded once to fp32): a lag t in
+ *              TMIN .. TMAX - 1 with v[t] < v[t - 1], v[t] <= v[t + 1] and v[t] < threshold (as fp32); its integer cost is
+ *              q = min(1023, floor(1024 v[t])) + ((octave_cost (L[t] - L[TMIN])) >> 8), L[t] = round(256 log2 t) (an integer table
+ *              made on the host in double; no entry lies within 8e-4 of a rounding boundary).  The K candidates smallest by (q, t)
+ *              are kept and numbered 1 .. by ascending t; state 0 is "unvoiced" with cost unvoiced_cost
+ *   path       the states that minimise the sum of the state costs and of the transition costs between consecutive frames, in
+ *              integers: (jump_cost |L[t] - L[t']|) >> 8 between two voiced states, switch_cost between a voiced and the unvoiced
+ *              state, 0 between unvoiced states.  Ties go to the smaller predecessor state, at the last frame to the smaller state
+ *   output     a voiced frame with lag t: a, b, c = v[t - 1], v[t], v[t + 1]; den = (a - 2 b) + c; off = 0.5 (a - c) / den if
+ *              den > 0, else 0, clamped to +-0.5; f0 = 24000 / (t + off); strength = 1 - min(1, b).  An unvoiced frame: 0.0 and 0.0
+ * The device computes d, e, c and v in fp32, in this fixed order.  d[f] = (p[f] + p[f + 1]) + p[f + 2] from per-block partial sums
+ * p[b][t] = sum over j = 0 .. H - 1, ascending, one fused multiply-add per term, of (x[b H + j] - x[b H + j + t])^2, each computed once.
+ * e[f]: 64 strided sums (sample j goes to sum j mod 64, ascending, fused multiply-add), then a butterfly over the 64.  c[f][t]: the
+ * lags in 64 runs of 7 (run i = lags 7 i + 1 .. 7 i + 7); within a run the running sum in ascending order, across runs a
+ * Hillis-Steele scan of the run totals; c = (scan value of the runs before) + (running sum within the run).  v = (d t) / c with IEEE
+ * division.  Everything from the candidates to the path is integer and exact on those v; the totals are int32 with the smallest
+ * total subtracted once per 64 frames, which changes no decision.  The output step is fp32, den = fma(-2, b, a) + c.
+ *
+ * sopro_f0_rows_f32 runs the whole operator on the rows of a padded batch: wav fp32 [rows] rows row_stride apart (any alignment);
+ * lens int32 [rows] and params float [rows][SOPRO_F0_PARAMS] = (threshold, floor_db, octave_cost, jump_cost, switch_cost,
+ * unvoiced_cost) are HOST arrays, read before the call returns: 0 < threshold <= 1, -100 <= floor_db <= 0, octave_cost and
+ * unvoiced_cost integers in 0 .. SOPRO_F0_COST_MAX, jump_cost and switch_cost integers in 0 .. SOPRO_F0_JUMP_MAX.  With fcap =
+ * frames(max(lens)): f0, strength fp32 [rows] rows out_stride apart, frames f >= F of a row are left as they were; nvoiced device
+ * int32 [rows] (written for every row); dbg_v NULL or fp32 [rows][fcap][TMAX + 1], dbg_e NULL or fp32 [rows][fcap], dbg_cands NULL or
+ * int32 [rows][fcap][K] (the kept lags by ascending lag, 0 = none), all three for tests, frames f >= F left as they were.
+ * sopro_f0_paths runs candidates, path and output from a given v fp32 [rows][fcap][TMAX + 1] (finite, >= 0) and e fp32 [rows][fcap]
+ * on the device, frames int32 [rows] (host, 0 .. fcap): what sopro_f0_rows_f32 does after its front end, for tests of that half.
+ * ws: sopro_f0_workspace_bytes(rows, cap) bytes of device memory for cap = max(lens) (sopro_f0_paths: cap = SPAN + (fcap - 1) H),
+ * 4-byte aligned: per frame the K packed candidates, their three v values and one back-pointer word - v itself is never stored
+ * (-1: rows <= 0 or cap outside [0, 2^24]).
+ * Refused (-2, nothing launched): a NULL lens / frames, params, nvoiced or ws, rows outside 1 .. 65535, a length outside [0, 2^24],
+ * a parameter outside its range, with rows > 1 a stride below what a row reads or writes, ws_bytes too small.
+ * Per group of 64 rows three launches on `stream` - front (one workgroup per 8 frames: 10 blocks staged in LDS, a thread owns four
+ * lags of a block and slides the lagged samples through registers; then one wave per frame for e, the scan, v and the pick), path
+ * (one wave per row, frames in chunks of 64: the 5 x 5 step costs of a chunk in parallel, then the recursion; back-pointers in the
+ * workspace), out (one thread per frame);
+ * no float atomics, so a row has the same bits alone and in a batch, on any stream, and two calls give the same bits.  A call
+ * copies nothing to the host, allocates nothing and synchronises nothing. */
+#define SOPRO_F0_H 240
+#define SOPRO_F0_W 720
+#define SOPRO_F0_TMIN 48
+#define SOPRO_F0_TMAX 400
+#define SOPRO_F0_SPAN 1120
+#define SOPRO_F0_K 4
+#define SOPRO_F0_PARAMS 6
+#define SOPRO_F0_COST_MAX 1024
+#define SOPRO_F0_JUMP_MAX 4096
+int64_t sopro_f0_workspace_bytes(int32_t rows, int64_t cap);
+int sopro_f0_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens, const float* params, int32_t rows, float* f0, float* strength,
+                      int64_t out_stride, int32_t* nvoiced, float* dbg_v, float* dbg_e, int32_t* dbg_cands, void* ws, int64_t ws_bytes,
+                      void* stream);
+int sopro_f0_paths(const float* v, const float* e, const int32_t* frames, const float* params, int32_t rows, int32_t fcap, float* f0,
+                   float* strength, int64_t out_stride, int32_t* dbg_cands, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

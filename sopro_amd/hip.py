@@ -301,6 +301,9 @@ SYMBOLS = {
     "sopro_formant_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i32, _i32, _p, _i64, _i64, _p, _p, _i64, _p]),
     "sopro_crop_workspace_bytes": (_i64, [_i32, _i64]),
     "sopro_crop_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
+    "sopro_f0_workspace_bytes": (_i64, [_i32, _i64]),
+    "sopro_f0_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    "sopro_f0_paths": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p, _p, _i64, _p, _p, _i64, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -1880,6 +1883,102 @@ def speech_crop(wav: torch.Tensor, lens, params, win: int, *, out: Optional[torc
                 feats.append((host[b, 0, :F].contiguous().view(torch.float32).numpy().copy(), host[b, 1, :F].numpy().copy()) if c is not None else None)
             res.append(feats)
     return tuple(res)
+
+
+# ---- pitch tracking (sopro_f0_*; definition in include/sopro_hip.h, numpy restatement in tests/f0_ref.py; parameters in f0.py) ----
+F0_H, F0_W, F0_TMIN, F0_TMAX, F0_SPAN, F0_K, F0_PARAMS = 240, 720, 48, 400, 1120, 4, 6
+f0_calls = 0  # calls of sopro_f0_rows_f32 / sopro_f0_paths by this process: nothing else in the engine adds to it
+
+
+def _f0_params(params, rows: int):
+    from . import f0 as F0
+
+    ps = F0.per_row(params, rows, "params")
+    return (C.c_float * (F0_PARAMS * rows))(*[v for p in ps for v in p.as_floats()])
+
+
+def f0_track(wav: torch.Tensor, lens, params=None, *, debug: bool = False, f0: Optional[torch.Tensor] = None,
+             strength: Optional[torch.Tensor] = None):
+    """The fundamental frequency of every 10 ms frame of every row of a padded batch (sopro_f0_rows_f32): ``wav`` fp32 [rows, >=
+    max(lens)] on the device at 24 kHz (rows ``wav.stride(0)`` apart, any alignment), ``lens`` valid samples per row, ``params`` one
+    ``PitchParams`` or None (the defaults), or one per row -> (f0 fp32 [rows, fcap] in Hz with 0.0 = unvoiced, strength fp32 [rows,
+    fcap], nvoiced int32 [rows], frames) with frames[b] = 0 for lens[b] < 1120, else (lens[b] - 1120) // 240 + 1 (a host list) and
+    fcap = max(frames); all three tensors stay on the device, entries past a row's frames are not written (fresh buffers are zero,
+    given ``f0=`` / ``strength=`` buffers keep what they held).  Three launches per 64 rows on the current stream and no
+    synchronisation.  ``debug=True`` appends (v fp32 [rows, fcap, 401], e fp32 [rows, fcap], cands int32 [rows, fcap, 4]): the
+    normalised difference, the window energies and the kept lags (0 = none), for tests."""
+    from . import f0 as F0
+
+    global f0_calls
+    lens_h = _lens_list(lens)
+    rows = len(lens_h)
+    _check_rows(wav, lens_h, "f0_track")
+    if rows == 0:
+        raise SoproHipError("f0_track: at least one row")
+    par_c = _f0_params(params, rows)
+    cap = max(lens_h)
+    frames = [F0.frames_of(n) for n in lens_h]
+    fcap = max(frames)
+    dev = wav.device
+    _out_buffer(f0, rows, fcap, "f0_track")
+    _out_buffer(strength, rows, fcap, "f0_track")
+    lib = load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.sopro_f0_workspace_bytes(rows, cap))
+        if ws_bytes < 0:
+            raise SoproHipError(f"f0_track: {rows} rows of up to {cap} samples are outside the operator's range")
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.int32, device=dev)
+        if f0 is None:
+            f0 = torch.zeros(rows, max(1, fcap), dtype=torch.float32, device=dev)
+        if strength is None:
+            strength = torch.zeros(rows, max(1, fcap), dtype=torch.float32, device=dev)
+        if rows > 1 and f0.stride(0) != strength.stride(0):
+            raise SoproHipError("f0_track: f0 and strength must have the same row stride")
+        nvoiced = torch.empty(rows, dtype=torch.int32, device=dev)
+        dv = torch.zeros(rows, max(1, fcap), F0_TMAX + 1, dtype=torch.float32, device=dev) if debug else None
+        de = torch.zeros(rows, max(1, fcap), dtype=torch.float32, device=dev) if debug else None
+        dc = torch.zeros(rows, max(1, fcap), F0_K, dtype=torch.int32, device=dev) if debug else None
+        lens_c = (C.c_int32 * rows)(*lens_h)
+        f0_calls += 1
+        _check(lib.sopro_f0_rows_f32(ptr(wav), int(wav.stride(0)), lens_c, par_c, rows, ptr(f0), ptr(strength), int(f0.stride(0)),
+                                     ptr(nvoiced, torch.int32), ptr(dv), ptr(de), ptr(dc, torch.int32), ws.data_ptr(), ws_bytes, _stream()),
+               "sopro_f0_rows_f32")
+    res = (f0[:, :fcap], strength[:, :fcap], nvoiced, frames)
+    return res + (dv[:, :fcap], de[:, :fcap], dc[:, :fcap]) if debug else res
+
+
+def f0_paths(v: torch.Tensor, e: torch.Tensor, frames, params=None):
+    """Candidates, path and output of the pitch tracker from a given normalised difference (sopro_f0_paths): ``v`` fp32 [rows, fcap,
+    401] (finite, >= 0) and ``e`` fp32 [rows, fcap], contiguous and on the device, ``frames`` valid frames per row -> (f0 fp32 [rows,
+    fcap], strength fp32 [rows, fcap], cands int32 [rows, fcap, 4]); entries past a row's frames are zero.  What ``f0_track`` does
+    after its front end, for tests of that half.  Three launches per 64 rows on the current stream."""
+    global f0_calls
+    ptr(v)
+    ptr(e)
+    if v.dim() != 3 or int(v.shape[2]) != F0_TMAX + 1 or not v.is_contiguous() or tuple(e.shape) != tuple(v.shape[:2]) or not e.is_contiguous():
+        raise SoproHipError(f"f0_paths: v must be a contiguous fp32 [rows, fcap, {F0_TMAX + 1}] and e a contiguous fp32 [rows, fcap]")
+    rows, fcap = int(v.shape[0]), int(v.shape[1])
+    fr_h = _lens_list(frames)
+    if len(fr_h) != rows or (fr_h and (min(fr_h) < 0 or max(fr_h) > fcap)):
+        raise SoproHipError(f"f0_paths: one frame count in [0, {fcap}] per row ({rows})")
+    if rows == 0:
+        raise SoproHipError("f0_paths: at least one row")
+    par_c = _f0_params(params, rows)
+    dev = v.device
+    lib = load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.sopro_f0_workspace_bytes(rows, F0_SPAN + (fcap - 1) * F0_H if fcap > 0 else 0))
+        if ws_bytes < 0:
+            raise SoproHipError(f"f0_paths: {rows} rows of up to {fcap} frames are outside the operator's range")
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.int32, device=dev)
+        f0 = torch.zeros(rows, max(1, fcap), dtype=torch.float32, device=dev)
+        strength = torch.zeros(rows, max(1, fcap), dtype=torch.float32, device=dev)
+        dc = torch.zeros(rows, max(1, fcap), F0_K, dtype=torch.int32, device=dev)
+        fr_c = (C.c_int32 * rows)(*fr_h)
+        f0_calls += 1
+        _check(lib.sopro_f0_paths(ptr(v), ptr(e), fr_c, par_c, rows, fcap, ptr(f0), ptr(strength), int(f0.stride(0)), ptr(dc, torch.int32),
+                                  ws.data_ptr(), ws_bytes, _stream()), "sopro_f0_paths")
+    return f0[:, :fcap], strength[:, :fcap], dc[:, :fcap]
 
 
 # ---- word timestamps (sopro_align_*; definition in include/sopro_hip.h, restatement in tests/align_ref.py) ----

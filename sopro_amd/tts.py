@@ -445,6 +445,41 @@ class SoproTTS:
 
         return detect(wav, key, device=self.device)
 
+    @torch.inference_mode()
+    def pitch_track(self, wav, *, lens=None, params=None):
+        """New: the pitch of a waveform -> ``f0.PitchTrack`` (``f0`` in Hz per 10 ms frame with 0.0 = unvoiced, ``strength``,
+        ``centres``, ``median_hz``, ``voiced_fraction``, ``span``, ``semitones_to``).  ``wav``: [N] / [1, N] / [1, 1, N] on any device
+        (what ``synthesize`` returns), read as 24 kHz, the codec's rate and the only one supported; or a padded [rows, cap] with
+        ``lens=[...]`` -> a list of ``PitchTrack``, one per row.  ``params``: a ``sopro_amd.PitchParams`` (None: the defaults), or one
+        per row.  Runs on the bulk stream (``hip.f0_track``: the YIN difference, the candidate pick and an integer Viterbi path in
+        HIP) and synchronises it, so the track is ready when the call returns.  An offline analysis: it changes no audio."""
+        from . import f0 as F0
+        from . import hip
+
+        rows, lens_h, batched = F0.as_rows(wav, lens, self.device)
+        ps = F0.per_row(params, len(lens_h), "params")
+        if not lens_h:
+            return []
+        with self.model.on_stream(bulk=True):
+            hz, st, _nv, frames = hip.f0_track(rows, lens_h, ps)
+        self.model.bulk_stream.synchronize()
+        tracks = [F0.PitchTrack(hz[b, :n], st[b, :n]) for b, n in enumerate(frames)]
+        return tracks if batched else tracks[0]
+
+    @torch.inference_mode()
+    def voice_pitch(self, *, ref_audio_path: str, denoise=None, crop=None, ref_seconds: Optional[float] = None, params=None):
+        """New: the pitch of a reference voice -> the ``f0.PitchTrack`` of exactly the waveform the encoder would see for the same
+        arguments of ``prepare_reference`` (``MimiCodec.reference_waveform``: load, energy trim, resample, ``denoise``, the crop to
+        ``ref_seconds``, 12 s by default, at the centre or by ``crop``).  ``vp.semitones_to(110.0)`` is the ``pitch=`` that brings the
+        voice's median to 110 Hz."""
+        from . import crop as CR
+
+        if ref_seconds is None:
+            ref_seconds = 12.0
+        CR.refuse_without_window(crop, "voice_pitch", ref_seconds)
+        x = self.codec.reference_waveform(ref_audio_path, crop_seconds=ref_seconds if ref_seconds > 0 else None, denoise=denoise, crop=crop)
+        return self.pitch_track(x, params=params)
+
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""
         import wave

@@ -1,7 +1,7 @@
-"""Word timestamps, host side: from a frame-to-token path (``SoproTTSModel.align_batch``) to word cues in samples.
+"""Word timestamps, host side: from a frame-to-token path (``replay.align_batch`` / ``replay.AlignStream``) to word cues in samples.
 
 Pure Python, importable without a device.  The device half (attention maps of the AR generator's text cross-attention, the best
-monotonic path through them) is defined in DESIGN.md "Word timestamps" and include/sopro_hip.h.
+monotonic path through them) is ``sopro_amd/replay.py``, defined in DESIGN.md "Word timestamps" and include/sopro_hip.h.
 
     Alignment   what the engine knows about one utterance, in frames
     token_spans character range of every token id ``encode_text`` returns (BOS / EOS: empty)

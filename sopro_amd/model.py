@@ -711,276 +711,24 @@ class SoproTTSModel:
         return [toks[b, : lens[b]] for b in range(B)]
 
     # ------------------------------------------------------------------ word timestamps
-    def _align_operands(self) -> Dict[str, Any]:
-        """The AR stack's weights in the layouts of the full-sequence operators (made once, at the first timed call): the GLU
-        projection packed per 64 rows as the contraction's gating epilogue reads it (pack.pack_glu; the engine keeps the natural
-        layout for the frame kernels), everything else as it is.  The RMSNorm weights are folded into the projections that follow
-        (pack.py), so the norms of the replay run with a vector of ones."""
-        ops = getattr(self, "_align_ops", None)
-        if ops is None:
-            from .pack import pack_glu
-
-            w, dev = self.w, self.device
-            ops = {"ones": torch.ones(self.D, device=dev), "col": _i32([0], dev), "off": _i32([0], dev), "wq": torch.ones(1, device=dev)}
-            for i in range(len(self.cfg.ar_dilations)):
-                ops[f"glu.{i}"] = tuple(t.contiguous() for t in pack_glu(w[f"ar.blocks.{i}.glu.w"], w[f"ar.blocks.{i}.glu.b"]))
-            self._align_ops = ops  # (shared by the lanes of clone_lane: read-only)
-        return ops
-
+    # (the device half lives in sopro_amd/replay.py; it is imported where it is used, because that module imports this one)
     def _align_heads(self, heads) -> Dict[int, int]:
-        """(layer, head) pairs -> head mask per attention layer; ``None``: every head of every layer."""
-        layers = tuple(int(i) for i in self.cfg.ar_xattn_layers)
-        if heads is None:
-            return {i: 0xF for i in layers}
-        masks = {i: 0 for i in layers}
-        for pair in heads:
-            try:
-                l, h = (int(v) for v in pair)
-            except (TypeError, ValueError):
-                raise ValueError(f"align_heads wants (layer, head) pairs, got {pair!r}") from None
-            if l not in masks or not 0 <= h < 4:
-                raise ValueError(f"align_heads: layer must be one of {layers} and head in [0, 4), got {(l, h)}")
-            masks[l] |= 1 << h
-        if not any(masks.values()):
-            raise ValueError("align_heads selects no head")
-        return masks
+        """(layer, head) pairs -> head mask per attention layer; ``None``: every head of every layer (``replay.select_heads``)."""
+        from .replay import select_heads
 
-    @torch.inference_mode()
+        return dict(select_heads(self.cfg.ar_xattn_layers, heads).masks)
+
     def align_batch(self, prep: Dict[str, Any], state: Dict[str, Any], heads=None) -> List["Alignment"]:
-        """Word timing's device half, a post-pass over a finished AR phase (DESIGN.md "Word timestamps"): the AR stack is replayed
-        teacher-forced over all frames at once on the generated codebook-0 tokens (oracle ``ar_forward_teacher`` without the head),
-        ``sopro_align_scores_f32`` turns the three cross-attention layers' queries and keys into log mean attention, and
-        ``sopro_align_dp_f32`` finds each row's best monotonic path -> one ``Alignment`` per row, in frames.  Runs on the bulk stream;
-        ``prep`` (conditioning: ``txt_seq``, ``text_lens``, ``text_lens_host``) and ``state`` (phase_ar: ``cond_ar``, ``hist``,
-        ``lens``) are only read.  ``heads``: the (layer, head) pairs to average, default all 12.  The score matrix of the last call
-        stays in ``self.align_last`` ([B, T, S] on the device, valid until the next call)."""
-        from .align import Alignment
+        """Word timing as a post-pass over a finished AR phase -> one ``Alignment`` per row: see ``replay.align_batch``."""
+        from . import replay
 
-        cfg, w, dev, D = self.cfg, self.w, self.device, self.D
-        masks = self._align_heads(heads)
-        n_sel = sum(bin(v).count("1") for v in masks.values())
-        lens_t = [int(n) for n in state["lens"]]
-        lens_s = [int(n) for n in prep["text_lens_host"]]
-        B, S = int(state["B"]), int(prep["txt_seq"].shape[1])
-        hist, cond = state["hist"], state["cond_ar"]
-        Tp = min(max(8, -(-max(lens_t) // 8) * 8), int(hist.shape[1]), int(cond.shape[1]))
-        M = B * Tp
-        ops = self._align_operands()
-        ksz = int(cfg.ar_kernel)
-        layers = [int(i) for i in cfg.ar_xattn_layers]
-        last = max(i for i in layers if masks[i])  # nothing after this layer's queries is needed
-        modes = {i: (0 if n == 0 else (2 if n == len(layers) - 1 else 1)) for n, i in enumerate(layers)}
-        get = self.ws.get
-        with self.on_stream(bulk=True):
-            lens_d = torch.tensor([lens_t, lens_s], dtype=torch.int32).to(dev)
-            tl, sl = lens_d[0], lens_d[1]
-            tok = get("align.tok", (B, Tp), dtype=torch.int32)
-            tok[:, 0] = int(cfg.bos_row)
-            if Tp > 1:
-                tok[:, 1:] = hist[:, : Tp - 1].clamp(0, self.V - 1)  # (codes past a row's own length are never used: the stack is causal)
-            xa, xb, nb = get("align.xa", (M, D)), get("align.xb", (M, D)), get("align.n", (M, D))
-            g, f = get("align.g", (M, D)), get("align.f", (M, 4 * D))
-            xb.view(B, Tp, D).copy_(cond[:, :Tp])
-            hip.codebook_sum(tok, 1, ops["col"], ops["off"], ops["wq"], w["cb_embed"], xa, rows=M, D=D, base=xb, alpha=1.0, beta=1.0)
-            acc = get("align.acc", (B, Tp, S))
-            x, y = xa, xb
-            ts = prep["txt_seq"].to(dev).float().contiguous().view(B * S, D)
-            nkv, kv = get("align.nkv", (B * S, D)), get("align.kv", (B * S, 2 * D))
-            q, att = get("align.q", (M, D)), get("align.att", (M, D))
-            for i, dil in enumerate(cfg.ar_dilations):
-                p = f"ar.blocks.{i}"
-                gw, gb = ops[f"glu.{i}"]
-                hip.norm(x, nb, ops["ones"], rows=M, C_=D, eps=RMS_EPS)
-                hip.gemm(nb, gw, g, M=M, N=2 * D, K=D, bias=gb, epilogue=hip.EPI_GLU)
-                hip.dwconv(g, w[p + ".dw.w"], w[p + ".dw.b"], y, B=B, T=Tp, C_=D, ksize=ksz, dil=int(dil), left=(ksz - 1) * int(dil), mode=1, res=x)
-                hip.norm(y, nb, ops["ones"], rows=M, C_=D, eps=RMS_EPS)
-                hip.gemm(nb, w[p + ".ff1.w"], f, M=M, N=4 * D, K=D, bias=w[p + ".ff1.b"], epilogue=hip.EPI_GELU)
-                hip.gemm(f, w[p + ".ff2.w"], x, M=M, N=D, K=4 * D, bias=w[p + ".ff2.b"], epilogue=hip.EPI_RES, R=y)
-                if i not in masks:
-                    continue
-                pa = f"ar.x_attns.{i}"
-                hip.norm(ts, nkv, w[pa + ".nkv.weight"], rows=B * S, C_=D, eps=RMS_EPS)
-                hip.gemm(nkv, w[pa + ".kv.w"], kv, M=B * S, N=2 * D, K=D)
-                hip.norm(x, nb, ops["ones"], rows=M, C_=D, eps=RMS_EPS)
-                hip.gemm(nb, w[pa + ".qa.w"], q, M=M, N=D, K=D)  # (qa.w = q_proj with RMSNorm_nq's weight folded in)
-                hip.align_scores(q, kv, tl, sl, acc, head_mask=masks[i], weight=1.0 / n_sel, mode=modes[i], H=4, ldq=D, ldk=2 * D,
-                                 q_bstride=Tp * D, k_bstride=S * 2 * D)
-                if i == last:
-                    break
-                hip.attention(q, kv, kv, att, B=B, H=4, dh=D // 4, Tq=Tp, Tk=S, ldq=D, ldk=2 * D, ldv=2 * D, ldo=D, q_bstride=Tp * D,
-                              k_bstride=S * 2 * D, v_bstride=S * 2 * D, o_bstride=Tp * D, klens=sl, v_off=D)
-                hip.gemm(att, w[pa + ".o.w"], y, M=M, N=D, K=D, epilogue=hip.EPI_RES, R=x, scale=w[pa + ".gate_scale"])
-                x, y = y, x
-            for i in layers:  # the layers past the last selected one add nothing; the last launch still finishes the scores
-                if i > last:
-                    hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=modes[i], H=4, ldq=D, ldk=2 * D, q_bstride=Tp * D,
-                                     k_bstride=S * 2 * D)
-            if len(layers) == 1:  # (one attention layer: its launch wrote the sum, a second one finishes it)
-                hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=2, H=4, ldq=D, ldk=2 * D, q_bstride=Tp * D, k_bstride=S * 2 * D)
-            dws = get("align.dp_ws", (max(1, int(hip.load().sopro_align_ws_bytes(B, Tp, S)) // 8),), dtype=torch.int64)
-            out = get("align.out", (B * Tp + B * S * 2 + 2 * B,), dtype=torch.int32)  # path | bounds | total | status: one download
-            out.zero_()
-            path, bounds = out[: B * Tp].view(B, Tp), out[B * Tp: B * Tp + 2 * B * S].view(B, S, 2)
-            total, status = out[B * Tp + 2 * B * S: B * Tp + 2 * B * S + B].view(torch.float32), out[B * Tp + 2 * B * S + B:]
-            hip.align_paths(acc, tl, sl, path=path, bounds=bounds, total=total, status=status, ws=dws)
-            host = out.cpu()
-        self.align_last = acc
-        hp = host[: B * Tp].view(B, Tp).tolist()
-        hb = host[B * Tp: B * Tp + 2 * B * S].view(B, S, 2).tolist()
-        ht = host[B * Tp + 2 * B * S: B * Tp + 2 * B * S + B].view(torch.float32).tolist()
-        hs = host[B * Tp + 2 * B * S + B:].tolist()
-        return [Alignment(path=hp[b][: lens_t[b]], token_frames=[tuple(v) for v in hb[b][: lens_s[b]]], total=float(ht[b]), status=int(hs[b]))
-                for b in range(B)]
+        return replay.align_batch(self, prep, state, heads)
 
     def align_stream(self, prep: Dict[str, Any], *, max_frames: int, lag_frames: int, chunk_frames: int, heads=None) -> "AlignStream":
-        """Word timing for one utterance while it is generated: see ``AlignStream``."""
+        """Word timing for one utterance while it is generated: see ``replay.AlignStream``."""
+        from .replay import AlignStream
+
         return AlignStream(self, prep, max_frames=max_frames, lag_frames=lag_frames, chunk_frames=chunk_frames, heads=heads)
-
-
-class AlignStream:
-    """``align_batch`` for a stream (DESIGN.md "Word timestamps", online form).  At open the text keys of every attention layer in
-    use are computed once.  ``step(hist, t1, final)`` replays the AR stack with ``align_batch``'s launch sequence over the window
-    rows [ws, t1), ws = max(0, t0 - (rf_ar - 1)) with t0 the frames scored so far - exact for the rows from t0 on, because the causal
-    depthwise convolution is the stack's only temporal operator -, writes the score rows [t0, t1) into a persistent
-    [1, max_frames + 1, S] buffer (``sopro_align_scores_f32`` with the queries offset to row t0 - ws), runs one
-    ``sopro_align_online_f32`` step and downloads the row's state and path.  The window is padded to a multiple of 8 and to at least
-    16 rows, so that the cross-attention always runs on the kernel ``align_batch`` uses from 16 frames on.  Everything is queued on the
-    model's bulk stream; a step's scratch comes from the model's workspace under ``align.s_*`` names (a step ends with a download, so
-    no step reads another's), the score buffer, the text keys and the state belong to the stream object."""
-
-    def __init__(self, model: "SoproTTSModel", prep: Dict[str, Any], *, max_frames: int, lag_frames: int, chunk_frames: int, heads=None):
-        from .align import check_align_window
-
-        check_align_window(lag_frames, chunk_frames)
-        m, cfg, w, dev, D = model, model.cfg, model.w, model.device, model.D
-        self.m, self.lag, self.chunk = m, int(lag_frames), int(chunk_frames)
-        self.masks = m._align_heads(heads)
-        self.n_sel = sum(bin(v).count("1") for v in self.masks.values())
-        self.layers = [int(i) for i in cfg.ar_xattn_layers]
-        self.last = max(i for i in self.layers if self.masks[i])
-        self.modes = {i: (0 if n == 0 else (2 if n == len(self.layers) - 1 else 1)) for n, i in enumerate(self.layers)}
-        Sp = int(prep["txt_seq"].shape[1])
-        self.S = int(prep["text_lens_host"][0]) if prep.get("text_lens_host") is not None else Sp  # (one utterance's prep: no padding)
-        if int(prep["txt_seq"].shape[0]) != 1 or not 1 <= self.S <= Sp or Sp > hip.ALIGN_S_MAX:
-            raise ValueError(f"AlignStream: one utterance of 1..{hip.ALIGN_S_MAX} text positions, got {tuple(prep['txt_seq'].shape)}")
-        self.Sp = Sp
-        self.cond = prep["cond_ar"]
-        self.Tar = min(int(max_frames) + 1, int(self.cond.shape[1]))
-        self.halo = int(cfg.rf_ar()) - 1
-        self.Wmax = min(max(16, -(-(self.halo + self.chunk) // 8) * 8), max(self.Tar, 1))
-        self.ops = m._align_operands()
-        self.t0 = 0          # frames scored
-        self.c = -1          # frames committed - 1 (the device's ``c`` as of the last download)
-        self.state_host = (-1, -1, 0, 0)
-        self.base = 0.0
-        self.path: List[int] = []
-        get, Wm, Tar = m.ws.get, self.Wmax, self.Tar
-        with m.on_stream(bulk=True):
-            self.tok = get("align.s_tok", (1, Wm), dtype=torch.int32)
-            self.xa, self.xb, self.nb = get("align.s_xa", (Wm, D)), get("align.s_xb", (Wm, D)), get("align.s_n", (Wm, D))
-            self.g, self.f = get("align.s_g", (Wm, D)), get("align.s_f", (Wm, 4 * D))
-            self.q, self.att = get("align.s_q", (Wm, D)), get("align.s_att", (Wm, D))
-            # what lives as long as the stream is the stream's own: a later stream of this engine cannot write into it
-            self.acc = torch.empty(1, Tar, Sp, device=dev)
-            self.out = torch.tensor([-1, -1, 0, 0, 0] + [0] * Tar, dtype=torch.int32).to(dev)  # state | path: one download
-            self.state = self.out[: hip.ALIGN_STATE_WORDS].view(1, hip.ALIGN_STATE_WORDS)
-            self.pathd = self.out[hip.ALIGN_STATE_WORDS:].view(1, Tar)
-            ts = prep["txt_seq"].to(dev).float().contiguous().view(Sp, D)
-            nkv = get("align.s_nkv", (Sp, D))
-            self.kv: Dict[int, torch.Tensor] = {}
-            for i in self.layers:
-                if i > self.last:
-                    break
-                pa = f"ar.x_attns.{i}"
-                self.kv[i] = torch.empty(Sp, 2 * D, device=dev)
-                hip.norm(ts, nkv, w[pa + ".nkv.weight"], rows=Sp, C_=D, eps=RMS_EPS)
-                hip.gemm(nkv, w[pa + ".kv.w"], self.kv[i], M=Sp, N=2 * D, K=D)
-
-    def _scores(self, hist: Sequence[int], t0: int, t1: int, lens: torch.Tensor) -> None:
-        """Score rows [t0, t1) from the window [ws, ws + W) (on the bulk stream; ``lens`` = (t1 - t0, S, ...) on the device)."""
-        m, cfg, w, D, ops = self.m, self.m.cfg, self.m.w, self.m.D, self.ops
-        ws = max(0, t0 - self.halo)
-        W = min(max(16, -(-(t1 - ws) // 8) * 8), self.Wmax)
-        if ws + W > self.Tar:  # (the padding rows must be rows of the conditioning: more left context instead)
-            ws = max(0, self.Tar - W)
-            W = self.Tar - ws
-        if t1 - ws > W:
-            raise ValueError(f"AlignStream: a step of {t1 - t0} frames (opened for {self.chunk})")
-        V, bos = m.V, int(cfg.bos_row)
-        rows = [bos if ws + r == 0 else (min(max(int(hist[ws + r - 1]), 0), V - 1) if ws + r - 1 < t1 else 0) for r in range(W)]
-        self.tok[:, :W].copy_(torch.tensor([rows], dtype=torch.int32), non_blocking=False)
-        xa, xb, nb, g, f, q, att = self.xa, self.xb, self.nb, self.g, self.f, self.q, self.att
-        xb[:W].copy_(self.cond[0, ws: ws + W])
-        hip.codebook_sum(self.tok, 1, ops["col"], ops["off"], ops["wq"], w["cb_embed"], xa, rows=W, D=D, base=xb, alpha=1.0, beta=1.0)
-        ksz = int(cfg.ar_kernel)
-        tl, sl = lens[0:1], lens[1:2]
-        acc = self.acc[:, t0:t1]
-        qo = (t0 - ws) * D
-        x, y = xa, xb
-        kv = None
-        for i, dil in enumerate(cfg.ar_dilations):
-            p = f"ar.blocks.{i}"
-            gw, gb = ops[f"glu.{i}"]
-            hip.norm(x, nb, ops["ones"], rows=W, C_=D, eps=RMS_EPS)
-            hip.gemm(nb, gw, g, M=W, N=2 * D, K=D, bias=gb, epilogue=hip.EPI_GLU)
-            hip.dwconv(g, w[p + ".dw.w"], w[p + ".dw.b"], y, B=1, T=W, C_=D, ksize=ksz, dil=int(dil), left=(ksz - 1) * int(dil), mode=1, res=x)
-            hip.norm(y, nb, ops["ones"], rows=W, C_=D, eps=RMS_EPS)
-            hip.gemm(nb, w[p + ".ff1.w"], f, M=W, N=4 * D, K=D, bias=w[p + ".ff1.b"], epilogue=hip.EPI_GELU)
-            hip.gemm(f, w[p + ".ff2.w"], x, M=W, N=D, K=4 * D, bias=w[p + ".ff2.b"], epilogue=hip.EPI_RES, R=y)
-            if i not in self.masks:
-                continue
-            pa = f"ar.x_attns.{i}"
-            kv = self.kv[i]
-            hip.norm(x, nb, ops["ones"], rows=W, C_=D, eps=RMS_EPS)
-            hip.gemm(nb, w[pa + ".qa.w"], q, M=W, N=D, K=D)
-            hip.align_scores(q, kv, tl, sl, acc, head_mask=self.masks[i], weight=1.0 / self.n_sel, mode=self.modes[i], H=4, ldq=D, ldk=2 * D,
-                             q_bstride=W * D, k_bstride=self.Sp * 2 * D, q_off=qo)
-            if i == self.last:
-                break
-            hip.attention(q, kv, kv, att, B=1, H=4, dh=D // 4, Tq=W, Tk=self.Sp, ldq=D, ldk=2 * D, ldv=2 * D, ldo=D, q_bstride=W * D,
-                          k_bstride=self.Sp * 2 * D, v_bstride=self.Sp * 2 * D, o_bstride=W * D, klens=sl, v_off=D)
-            hip.gemm(att, w[pa + ".o.w"], y, M=W, N=D, K=D, epilogue=hip.EPI_RES, R=x, scale=w[pa + ".gate_scale"])
-            x, y = y, x
-        for i in self.layers:  # (as in align_batch: the last launch finishes the scores)
-            if i > self.last:
-                hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=self.modes[i], H=4, ldq=D, ldk=2 * D, q_bstride=W * D,
-                                 k_bstride=self.Sp * 2 * D, q_off=qo)
-        if len(self.layers) == 1:
-            hip.align_scores(q, kv, tl, sl, acc, head_mask=0, weight=0.0, mode=2, H=4, ldq=D, ldk=2 * D, q_bstride=W * D,
-                             k_bstride=self.Sp * 2 * D, q_off=qo)
-
-    @torch.inference_mode()
-    def step(self, hist: Sequence[int], t1: int, final: bool) -> List[int]:
-        """Frames [0, t1) of the codebook-0 history ``hist`` are in (t1 never decreases; ``final``: no more will come) -> the path
-        positions of the frames this step committed.  ``state_host`` = (c, p, status, e), ``base`` and ``path`` follow."""
-        t1 = min(int(t1), self.Tar)
-        t0 = self.t0
-        if t1 < t0:
-            raise ValueError(f"AlignStream: t1 = {t1} after {t0} frames were scored")
-        if t1 - (self.c + 1) > hip.ALIGN_WINDOW_MAX:
-            raise ValueError(f"AlignStream: {t1 - (self.c + 1)} uncommitted frames, at most {hip.ALIGN_WINDOW_MAX}")
-        if t1 == 0 or (t1 == t0 and not final):
-            return []
-        nw = hip.ALIGN_STATE_WORDS
-        with self.m.on_stream(bulk=True):
-            lens = torch.tensor([t1 - t0, self.S, t1, 1 if final else 0], dtype=torch.int32).to(self.m.device)
-            if t1 > t0:
-                self._scores(hist, t0, t1, lens)
-                self.t0 = t1
-            hip.align_online(self.acc, lens[2:3], lens[1:2], lens[3:4], self.lag, self.state, self.pathd)
-            host = self.out[: nw + t1].cpu()
-        c, p, status, e = (int(v) for v in host[:4].tolist())
-        self.base = float(host[4:5].view(torch.float32)[0])
-        new = host[nw + self.c + 1: nw + c + 1].tolist()
-        self.c, self.state_host = c, (c, p, status, e)
-        self.path += new
-        if final:
-            self.m.align_last = self.scores()  # (as after align_batch: the score matrix of the last timed call)
-        return new
-
-    def scores(self) -> torch.Tensor:
-        """The score rows written so far, [1, t0, S] on the device (a view of the persistent buffer)."""
-        return self.acc[:, : self.t0, : self.S]
 
 
 class _PhaseTimer:
@@ -1336,3 +1084,6 @@ class _ARRun:
             hb.copy_from(plan.first_eos)  # a kernel of the library writes the page-locked words
         m.stream.synchronize()
         return h, hb.values()
+
+
+from .replay import AlignStream  # noqa: E402,F401  (its home since the replay moved; down here because replay.py imports this module)

@@ -107,7 +107,7 @@ class SoproTTSStreamer:
                      speed: float = 1.0, pitch: float = 0.0, watermark=None, denoise=None, report: Optional[list] = None, crop=None,
                      formant: Optional[float] = None):
         """``stream`` with word cues (``SoproTTS.stream_timed``): the same sampler draws, chunks and effects chain, and after every
-        chunk's decode one step of ``model.AlignStream`` on the frames generated so far.  Yields ``align.TimedChunk``; the words of an
+        chunk's decode one step of ``replay.AlignStream`` on the frames generated so far.  Yields ``align.TimedChunk``; the words of an
         item are those the step closed, mapped through ``speed`` / ``pitch`` like ``synthesize_timed``'s.  The aligner steps at every
         multiple of ``chunk_frames`` (not final: whether the utterance ends there is only known a frame later) and once more, final,
         when the generator stops.  The loop is ``stream``'s, written out again rather than shared, so that ``stream`` runs the code

@@ -1,5 +1,5 @@
 """CPU restatement of the word-timestamp contract (DESIGN.md "Word timestamps", include/sopro_hip.h "word timestamps"): the yardstick
-the GPU tests compare ``hip.align_scores`` / ``hip.align_paths`` / ``SoproTTSModel.align_batch`` with.  Written from the definition;
+the GPU tests compare ``hip.align_scores`` / ``hip.align_paths`` / ``SoproTTSModel.align_batch`` (sopro_amd/replay.py) with.  Written from the definition;
 it shares no code with sopro_amd/.  The recurrence and the backtrack are numpy fp32, one frame at a time; the teacher-forced replay is plain
 torch in a dtype of the caller's choice (float32: the contract; float64: the error model the tests derive their tolerances from).
 tests/test_align_host.py checks ``dp`` against brute-force enumeration and ``replay`` against the oracle's own blocks."""

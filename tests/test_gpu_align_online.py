@@ -131,7 +131,8 @@ def _char_tok(tts, text):
 
 def test_incremental_scores_equal_align_batch(tts_noeos, cfg):
     """``AlignStream`` over a fixed greedy history of more than 150 frames in chunks of 6 (from frame 138 on the window starts past
-    frame 0: the halo), then ``align_batch`` over the same history: the same score rows, bit for bit."""
+    frame 0: the halo), then ``align_batch`` over the same history: the same score rows, bit for bit - for every head, for heads of
+    the first attention layer alone (the layers past it only finish the scores) and for one head of the last layer."""
     tts = tts_noeos
     model = tts.model
     ids = torch.tensor([1 + (7 * i) % 500 for i in range(23)])
@@ -143,25 +144,29 @@ def test_incremental_scores_equal_align_batch(tts_noeos, cfg):
     assert T >= 150 and int(cfg.rf_ar()) - 1 + 6 < T
     prep = model.prepare_conditioning(ids, ref, max_frames=max_frames, style_strength=float(cfg.style_strength))
     S = int(prep["txt_seq"].shape[1])
-    al = model.align_stream(prep, max_frames=max_frames, lag_frames=8, chunk_frames=6)
-    n0 = hip.align_calls
-    rows = O.Online(S, 8)
-    for t1, final in O.schedule(T, 6, stream=True):
-        new = al.step(hist, t1, final)
-        got = al.scores()[0].cpu().numpy()
-        assert got.shape == (t1, S)
-        assert new == rows.step(got, t1, final), t1      # the path through the rows scored so far, as the restatement walks it
-        assert al.state_host == rows.state() and np.float32(al.base).tobytes() == np.float32(rows.base).tobytes()
-    assert hip.align_calls > n0 and al.path == rows.path and len(al.path) == T
-    streamed = al.scores()[0].cpu().clone()
     hist_d = torch.zeros(1, max_frames + 1, dtype=torch.long, device=DEV)
     hist_d[0, :T] = torch.tensor(hist)
-    model.align_batch({"txt_seq": prep["txt_seq"], "text_lens_host": [S]}, {"lens": [T], "B": 1, "hist": hist_d, "cond_ar": prep["cond_ar"]})
-    whole = model.align_last[0, :T, :S].cpu()
-    diff = float((streamed - whole).abs().max())
-    print(f"T = {T}, S = {S}: streamed score rows against align_batch, max |d| = {diff:.3e}")
-    assert torch.allclose(whole.exp().sum(-1), torch.ones(T), atol=1e-4)
-    assert torch.equal(streamed, whole)
+    for heads in (None, [(1, 0), (1, 3)], [(5, 2)]):
+        al = model.align_stream(prep, max_frames=max_frames, lag_frames=8, chunk_frames=6, heads=heads)
+        n0 = hip.align_calls
+        rows = O.Online(S, 8)
+        for t1, final in O.schedule(T, 6, stream=True):
+            new = al.step(hist, t1, final)
+            if heads is not None:
+                continue
+            got = al.scores()[0].cpu().numpy()
+            assert got.shape == (t1, S)
+            assert new == rows.step(got, t1, final), t1      # the path through the rows scored so far, as the restatement walks it
+            assert al.state_host == rows.state() and np.float32(al.base).tobytes() == np.float32(rows.base).tobytes()
+        assert hip.align_calls > n0 and len(al.path) == T and (heads is not None or al.path == rows.path)
+        streamed = al.scores()[0].cpu().clone()
+        model.align_batch({"txt_seq": prep["txt_seq"], "text_lens_host": [S]}, {"lens": [T], "B": 1, "hist": hist_d, "cond_ar": prep["cond_ar"]},
+                          heads=heads)
+        whole = model.align_last[0, :T, :S].cpu()
+        diff = float((streamed - whole).abs().max())
+        print(f"heads {heads}, T = {T}, S = {S}: streamed score rows against align_batch, max |d| = {diff:.3e}")
+        assert torch.allclose(whole.exp().sum(-1), torch.ones(T), atol=1e-4), heads
+        assert torch.equal(streamed, whole), heads
 
 
 TEXT = "  so, streamed word timing works !"

@@ -1352,6 +1352,34 @@ int sopro_f0_rows_f32(const float* wav, int64_t row_stride, const int32_t* lens,
 int sopro_f0_paths(const float* v, const float* e, const int32_t* frames, const float* params, int32_t rows, int32_t fcap, float* f0,
                    float* strength, int64_t out_stride, int32_t* dbg_cands, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- voice similarity: ragged, batched Token2SV and the cosine of speaker vectors (kernels in csrc/spk.hip; numpy restatement in
+ * tests/spk_ref.py).
+ *
+ * sopro_spk_embed_rows: the unit speaker vector of every row of a padded token batch - Token2SV (src/sopro/nn/speaker.py:37-61:
+ * codebook mix 48-54, two depthwise convs + GELU 23-29 with src/sopro/nn/blocks.py:63-74, attentive statistics pooling
+ * blocks.py:174-188, proj + F.normalize speaker.py:60-61) - with every row computed as its OWN UNPADDED utterance (lengths == T,
+ * the form src/sopro/model.py:158-159 gives sv_ref and sopro_ref_prepare restates): frames outside [0, lens[r]) are zero in front
+ * of BOTH convs.  (The reference's padded batch path, speaker.py:43-57, masks before the first conv and after the second only, so
+ * its rows differ from their unpadded selves within three frames of their ends.)
+ * tokens int32 [rows][>= t_cap][Q], rows row_stride ELEMENTS apart, any alignment; lens int32 [rows] ON THE DEVICE, clamped to
+ * [0, t_cap]; tokens of frames >= lens[r] are never read.  sv fp32 [rows][sv_student_dim], rows sv_stride elements apart; a row
+ * with lens[r] == 0 gets a zero vector.  dbg_h fp32 [rows][t_cap][SD] / dbg_logit fp32 [rows][t_cap] (NULL, or 16-byte aligned /
+ * any): the encoder output and the pooling logit of frames t < lens[r]; other entries are not written.  ws:
+ * sopro_spk_workspace_bytes(e, rows, t_cap) bytes of device memory (256-byte aligned).  Two launches for any number of rows on
+ * `stream`, no host synchronisation, fixed-order reductions (two calls give the same bits).  fp32 in both precision modes.
+ * SOPRO_SPK_TILE_FRAMES (sopro_spk_tile_frames()) frames of one row are one workgroup of the first launch.
+ *
+ * sopro_spk_cosine: out = a . b / max(|a| |b|, 1e-12) of fp32 vectors of `dim` elements, rows a_stride / b_stride elements apart.
+ * bank == 0: a[i] with b[i] -> out[na] (na == nb); bank == 1: every a[i] with every b[n] -> out[na][nb].  The norms are recomputed
+ * (the vectors need not be unit); a zero vector gives 0.0. */
+#define SOPRO_SPK_TILE_FRAMES 32
+int32_t sopro_spk_tile_frames(void);
+int64_t sopro_spk_workspace_bytes(const sopro_engine* e, int32_t rows, int32_t t_cap);
+int sopro_spk_embed_rows(sopro_engine* e, void* ws, const int32_t* tokens, int64_t row_stride, const int32_t* lens, int32_t rows, int32_t t_cap,
+                         float* sv, int64_t sv_stride, float* dbg_h, float* dbg_logit, void* stream);
+int sopro_spk_cosine(const float* a, int64_t a_stride, int32_t na, const float* b, int64_t b_stride, int32_t nb, int32_t dim, int32_t bank,
+                     float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,13 @@ int sopro_stream_batch_append(float* cur, float* other, const float* qkv, int32_
                               int32_t nkeep, hipStream_t s);
 int sopro_stream_batch_gather(float* kv, const int32_t* keep, int32_t n_keep, int32_t layers, int32_t rows_cap, int64_t bstride, int32_t hs, int32_t half,
                               int32_t kv_len, hipStream_t s);
+// (spk.hip) the two launches of the ragged Token2SV
+int sopro_spk_frames_launch(const int32_t* tok, int64_t row_stride, int32_t Q, const int32_t* col, const int32_t* off, const float* cw, const float* emb,
+                            int64_t table_rows, int32_t SD, const float* w0, const float* b0, const float* w3, const float* b3, const float* W1,
+                            const float* b1, const float* w2, const float* b2, const int32_t* lens, int32_t rows, int32_t t_cap, float* h_ws,
+                            float* lg_ws, float* dbg_h, float* dbg_lg, hipStream_t s);
+int sopro_spk_pool_launch(const float* h_ws, const float* lg_ws, const int32_t* lens, int32_t rows, int32_t t_cap, int32_t SD, const float* Wp,
+                          const float* bp, int32_t svd, float* sv, int64_t sv_stride, hipStream_t s);
 
 namespace {
 
@@ -809,6 +816,44 @@ int sopro_ref_prepare(sopro_engine* e, void* workspace, const int32_t* tokens, i
     STG(gemm(s, w.nkv, wk, nullptr, kv[i], gk));
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ voice similarity (kernels: spk.hip)
+struct SpkWs { float *h, *lg; };
+static size_t spk_carve(const sopro_engine* e, SpkWs& w, void* ws, int rows, int t_cap) {
+  const size_t SD = e->t.count("token2sv.emb") ? (size_t)e->t.at("token2sv.emb").shape[1] : 0;
+  Carver cv(ws);
+  w.h = cv.take<float>((size_t)rows * t_cap * SD);
+  w.lg = cv.take<float>((size_t)rows * t_cap);
+  return cv.off;
+}
+
+int64_t sopro_spk_workspace_bytes(const sopro_engine* e, int32_t rows, int32_t t_cap) {
+  if (!e || rows <= 0 || t_cap <= 0) return 0;
+  SpkWs w;
+  return (int64_t)spk_carve(e, w, nullptr, rows, t_cap);
+}
+
+int sopro_spk_embed_rows(sopro_engine* e, void* ws, const int32_t* tokens, int64_t row_stride, const int32_t* lens, int32_t rows, int32_t t_cap,
+                         float* sv, int64_t sv_stride, float* dbg_h, float* dbg_logit, void* stream) {
+  SOPRO_CHECK_ARG(e && e->final && e->has_cond, "the engine must be finalized with the conditioning tensors first");
+  SOPRO_CHECK_ARG(ws && tokens && lens && sv, "ws, tokens, lens and sv must be non-NULL");
+  SOPRO_CHECK_ARG(rows > 0, "rows must be >= 1");
+  SOPRO_CHECK_ARG(t_cap > 0, "t_cap must be >= 1");
+  const sopro_engine_cfg& c = e->c;
+  const int Q = c.num_codebooks, SD = (int)e->t["token2sv.emb"].shape[1], svd = c.sv_student_dim;
+  SOPRO_CHECK_ARG(rows == 1 || row_stride >= (int64_t)t_cap * Q, "row_stride < t_cap * Q (rows must not overlap)");
+  SOPRO_CHECK_ARG(sv_stride >= svd, "sv_stride < sv_student_dim");
+  hipStream_t s = (hipStream_t)stream;
+  SpkWs w;
+  spk_carve(e, w, ws, rows, t_cap);
+  // ---- Token2SV up to the pooling logit (src/sopro/nn/speaker.py:48-57, src/sopro/nn/blocks.py:168-178), one workgroup per tile of frames
+  STG(sopro_spk_frames_launch(tokens, row_stride, Q, e->q_col, e->q_off, F(e, "token2sv.cw"), F(e, "token2sv.emb"), e->t["token2sv.emb"].shape[0], SD,
+                              F(e, "token2sv.enc.0.w"), F(e, "token2sv.enc.0.b"), F(e, "token2sv.enc.3.w"), F(e, "token2sv.enc.3.b"),
+                              F(e, "token2sv.pool.attn.0.w"), F(e, "token2sv.pool.attn.0.b"), F(e, "token2sv.pool.attn.2.w"),
+                              F(e, "token2sv.pool.attn.2.b"), lens, rows, t_cap, w.h, w.lg, dbg_h, dbg_logit, s));
+  // ---- pooling, proj, F.normalize (blocks.py:180-188, speaker.py:59-61), one workgroup per row
+  return sopro_spk_pool_launch(w.h, w.lg, lens, rows, t_cap, SD, F(e, "token2sv.proj.w"), F(e, "token2sv.proj.b"), svd, sv, sv_stride, s);
 }
 
 // ------------------------------------------------------------------------------------------------ autoregressive stage

@@ -304,6 +304,10 @@ SYMBOLS = {
     "sopro_f0_workspace_bytes": (_i64, [_i32, _i64]),
     "sopro_f0_rows_f32": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "sopro_f0_paths": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p, _p, _i64, _p, _p, _i64, _p]),
+    "sopro_spk_tile_frames": (_i32, []),
+    "sopro_spk_workspace_bytes": (_i64, [_p, _i32, _i32]),
+    "sopro_spk_embed_rows": (C.c_int, [_p, _p, _p, _i64, _p, _i32, _i32, _p, _i64, _p, _p, _p]),
+    "sopro_spk_cosine": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _i32, _i32, _p, _p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -2152,6 +2156,104 @@ def ref_prepare(engine, ws: torch.Tensor, tokens: torch.Tensor, T: int, sv: torc
         return
     ka = (C.c_void_p * len(kvs))(*[ptr(t) for t in kvs])
     _check(load().sopro_ref_prepare(engine, ptr(ws), ptr(tokens, torch.int32), T, ptr(sv), ptr(ref_seq), ka, _stream()), "sopro_ref_prepare")
+
+
+# ---- voice similarity (sopro_spk_*; definition in include/sopro_hip.h, numpy restatement in tests/spk_ref.py) ----
+spk_calls = 0  # calls of sopro_spk_embed_rows / sopro_spk_cosine by this process: nothing else in the engine adds to it
+
+
+def __getattr__(name: str):
+    if name == "SPK_TILE_FRAMES":  # frames of one row per workgroup of the ragged Token2SV: the library's own constant
+        return int(load().sopro_spk_tile_frames())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def spk_embed_rows(engine, tokens: torch.Tensor, lens, *, debug: bool = False, out: Optional[torch.Tensor] = None,
+                   ws: Optional[torch.Tensor] = None):
+    """The unit speaker vector of every row of a padded token batch (sopro_spk_embed_rows).  ``engine``: the model's
+    ``stages.EngineHandle`` (``model.eng``), or its raw handle together with ``out=``.  ``tokens`` int32 [rows, t_cap, Q] on the
+    device (frames contiguous, rows ``tokens.stride(0)`` apart, any alignment), ``lens`` valid frames per row - a host sequence
+    (uploaded here) or an int32 device tensor (used where it is: nothing on the host waits) -> sv fp32 [rows, sv_student_dim] on the
+    device.  Every row is Token2SV of its own ``tokens[b, :lens[b]]`` as an unpadded utterance; frames past ``lens[b]`` are never
+    read and a row of length 0 gives a zero vector.  ``out``: fp32 [rows, >= sv_student_dim] with contiguous rows to write into
+    (other entries keep what they held).  ``ws``: int32 scratch of at least ``sopro_spk_workspace_bytes`` (allocated otherwise).
+    Two launches on the current stream and no synchronisation.  ``debug=True`` -> (sv, h fp32 [rows, t_cap, SD], logit fp32 [rows,
+    t_cap]): the encoder output and the pooling logit, written for t < lens[b] only (zero elsewhere), for tests."""
+    global spk_calls
+    h = getattr(engine, "h", engine)
+    ptr(tokens, torch.int32)
+    if tokens.dim() != 3 or tokens.stride(2) != 1 or (int(tokens.shape[1]) > 1 and tokens.stride(1) != int(tokens.shape[2])):
+        raise SoproHipError(f"spk_embed_rows wants tokens int32 [rows, t_cap, Q] with contiguous frames, got {tuple(tokens.shape)} strides {tokens.stride()}")
+    rows, t_cap = int(tokens.shape[0]), int(tokens.shape[1])
+    dev = tokens.device
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+        if lens.dtype != torch.int32 or lens.dim() != 1 or int(lens.numel()) != rows or not lens.is_contiguous():
+            raise SoproHipError("spk_embed_rows: device lens must be a contiguous int32 vector with one entry per row")
+        lens_d = lens
+    else:
+        lens_h = _lens_list(lens)
+        if len(lens_h) != rows or (lens_h and (min(lens_h) < 0 or max(lens_h) > t_cap)):
+            raise SoproHipError(f"spk_embed_rows: one length in [0, {t_cap}] per row ({rows}), got {lens_h}")
+        lens_d = None
+    if rows == 0 or t_cap == 0:
+        raise SoproHipError("spk_embed_rows: at least one row and one frame of capacity")
+    lib = load()
+    with torch.cuda.device(dev):
+        if lens_d is None:
+            lens_d = torch.tensor(lens_h, dtype=torch.int32).to(dev, non_blocking=True)
+        ws_bytes = int(lib.sopro_spk_workspace_bytes(h, rows, t_cap))
+        if ws_bytes <= 0:
+            raise SoproHipError("spk_embed_rows: the engine holds no Token2SV tensors")
+        if ws is None:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+        elif ws.dtype != torch.int32 or not ws.is_cuda or ws.numel() * 4 < ws_bytes:
+            raise SoproHipError(f"spk_embed_rows: ws must be int32 on the device with at least {ws_bytes} bytes")
+        # the width of the speaker vector and of the encoder: the engine's own (a wrong guess here would be refused by the library)
+        svd = int(engine.sv_dim) if getattr(engine, "sv_dim", None) else None
+        if out is None:
+            if svd is None:
+                raise SoproHipError("spk_embed_rows: pass out= (the engine handle does not say how wide a speaker vector is)")
+            out = torch.zeros(rows, svd, dtype=torch.float32, device=dev)
+        else:
+            ptr(out)
+            if out.dim() != 2 or int(out.shape[0]) != rows or (int(out.shape[1]) > 1 and out.stride(1) != 1) or (svd is not None and int(out.shape[1]) < svd):
+                raise SoproHipError(f"spk_embed_rows: out must be fp32 [rows, >= sv_student_dim] with contiguous rows, got {tuple(out.shape)}")
+        dh = dl = None
+        if debug:
+            if not getattr(engine, "spk_width", None):
+                raise SoproHipError("spk_embed_rows(debug=True) wants the EngineHandle (it knows the encoder's width)")
+            sd = int(engine.spk_width)
+            dh = torch.zeros(rows, t_cap, sd, dtype=torch.float32, device=dev)
+            dl = torch.zeros(rows, t_cap, dtype=torch.float32, device=dev)
+        spk_calls += 1
+        _check(lib.sopro_spk_embed_rows(h, ws.data_ptr(), tokens.data_ptr(), int(tokens.stride(0)), lens_d.data_ptr(), rows, t_cap, ptr(out),
+                                        int(out.stride(0)), ptr(dh), ptr(dl), _stream()), "sopro_spk_embed_rows")
+    sv = out if svd is None else out[:, :svd]
+    return (sv, dh, dl) if debug else sv
+
+
+def spk_cosine(a: torch.Tensor, b: torch.Tensor, *, bank: bool = False) -> torch.Tensor:
+    """Cosine of speaker vectors (sopro_spk_cosine): ``a`` fp32 [na, dim], ``b`` fp32 [nb, dim] on the device with contiguous rows ->
+    fp32 [na] with a[i] . b[i] / max(|a[i]| |b[i]|, 1e-12) (``na == nb``), or with ``bank=True`` fp32 [na, nb] of every a[i] against
+    every b[n].  The norms are recomputed, so the vectors need not be unit; a zero vector gives 0.0.  One launch on the current
+    stream and no synchronisation."""
+    global spk_calls
+    ptr(a)
+    ptr(b)
+    for t, nm in ((a, "a"), (b, "b")):
+        if t.dim() != 2 or int(t.shape[0]) < 1 or int(t.shape[1]) < 1 or (int(t.shape[1]) > 1 and t.stride(1) != 1):
+            raise SoproHipError(f"spk_cosine: {nm} must be fp32 [n >= 1, dim >= 1] with contiguous rows, got {tuple(t.shape)}")
+    na, nb, dim = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+    if int(b.shape[1]) != dim or a.device != b.device:
+        raise SoproHipError(f"spk_cosine: a and b must have the same width and device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if not bank and na != nb:
+        raise SoproHipError(f"spk_cosine: pairwise mode wants as many rows in a as in b, got {na} and {nb} (bank=True compares every pair)")
+    with torch.cuda.device(a.device):
+        out = torch.empty((na, nb) if bank else (na,), dtype=torch.float32, device=a.device)
+        spk_calls += 1
+        _check(load().sopro_spk_cosine(ptr(a), int(a.stride(0)) if na > 1 else dim, na, ptr(b), int(b.stride(0)) if nb > 1 else dim, nb, dim,
+                                       1 if bank else 0, ptr(out), _stream()), "sopro_spk_cosine")
+    return out
 
 class Graph:
     """A recorded launch sequence (hipGraphExec) replayable on any stream."""

@@ -160,6 +160,7 @@ class LongformResult(NamedTuple):
     parts: Optional[List[LongformPart]] = None  # keep_parts=True
     edges: Optional[List[Tuple[int, int]]] = None  # keep_parts=True: (start, end) the join kept of every part
     words: Optional[List[Any]] = None          # word_cues=True: align.LongWordCue per word, samples in ``wav`` (accurate to one frame)
+    voice: Optional[List[Any]] = None          # voice_match=True: one voicematch.VoiceMatch per entry of ``segments``
 
 
 def join_params(trim_db: Optional[float], keep_ms: float, fade_ms: float) -> Dict[str, Any]:
@@ -228,8 +229,10 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
                     fade_ms: float = 5.0, plan: Union[str, Sequence[int]] = "throughput", max_rows: int = 32,
                     keep_parts: bool = False, speed: float = 1.0, word_cues: bool = False, token_spans=None, align_heads=None,
                     pitch: float = 0.0, watermark=None, silence=None, denoise=None, report: Optional[list] = None, crop=None,
-                    formant: Optional[float] = None) -> LongformResult:
-    """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``word_cues=True`` fills ``words``: one
+                    formant: Optional[float] = None, voice_match: bool = False) -> LongformResult:
+    """A text of any length -> one waveform (see ``SoproTTS.synthesize_long``).  ``voice_match=True`` fills ``voice``: one
+    ``VoiceMatch`` per segment, the speaker vector of the segment's generated tokens (each group's ``PaddedBatch.tokens`` over its
+    ``frames``) against the voice's ``sv_ref`` (``SoproTTS.voice_similarity``; three launches per group).  ``word_cues=True`` fills ``words``: one
     ``align.LongWordCue`` per word, character offsets relative to its segment's text, samples in the joined waveform
     (``offs[k] + (cue - edge_start)`` with the cue clamped to the range the join kept of segment k, after ``effects.map_cues`` has
     taken it through its row's rate, pitch and cut table).  ``token_spans``: a callable text -> [(start, end)] per token id for
@@ -251,16 +254,19 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     segs, groups, ref = _setup(tts, text, ref, ref_audio_path, ref_tokens_tq, ref_seconds, max_chars, plan, max_rows, denoise, report, crop)
     if not segs:
         return LongformResult(torch.zeros(1, 1, 0, device=tts.device), [], [], [] if keep_parts else None, [] if keep_parts else None,
-                              [] if word_cues else None)
+                              [] if word_cues else None, [] if voice_match else None)
     if word_cues:
         spans_of(segs[0].text)  # (a tokenizer without character offsets is refused before any segment runs)
     pieces, cues, parts, all_edges, base = [], [], [], [], 0
     words = [] if word_cues else None
+    voice = [] if voice_match else None
     for grp in _groups(tts, segs, groups, ref=ref, max_frames=max_frames, top_p=top_p, temperature=temperature, anti_loop=anti_loop,
                        style_strength=style_strength, min_gen_frames=min_gen_frames, seed=seed, pauses_ms=pauses_ms,
                        join_kw=join_params(trim_db, keep_ms, fade_ms), fx=rows, word_cues=word_cues, align_heads=align_heads):
         pieces.append(grp.piece)
         offs, edges = grp.offs.tolist(), grp.edges.tolist()
+        if voice_match:
+            voice.extend(tts.voice_similarity(ref=ref, tokens=grp.batch.tokens, lens=grp.batch.frames))
         for i, (s, e) in enumerate(edges):
             cues.append((segs[grp.first + i].text, base + offs[i], base + offs[i] + (e - s)))
             if word_cues:
@@ -276,7 +282,7 @@ def synthesize_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] =
     wav = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).reshape(1, 1, -1)
     if fx.watermark is not None:
         wav = effects.apply(wav.reshape(1, -1), [int(wav.shape[-1])], [effects.Effects(watermark=fx.watermark)])[0].reshape(1, 1, -1)
-    return LongformResult(wav, cues, groups, parts if keep_parts else None, all_edges if keep_parts else None, words)
+    return LongformResult(wav, cues, groups, parts if keep_parts else None, all_edges if keep_parts else None, words, voice)
 
 
 def stream_long(tts, text: str, *, ref=None, ref_audio_path: Optional[str] = None, ref_tokens_tq=None, ref_seconds: Optional[float] = None,

@@ -335,6 +335,30 @@ class SoproTTSModel:
         self.stream.synchronize()
         return sv
 
+    @torch.inference_mode()
+    def speaker_vectors(self, tokens_btq: torch.Tensor, lens) -> torch.Tensor:
+        """Speaker vectors of a padded batch, [B, T, Q] integer codes + valid frames per row -> [B, sv_student_dim] fp32 on the
+        device (new): Token2SV (src/sopro/nn/speaker.py:37-61) of every row as its own unpadded utterance - the form ``sv_ref`` has
+        (src/sopro/model.py:158-159) - in two launches for the whole batch (``hip.spk_embed_rows``, csrc/spk.hip); a row without
+        frames gives a zero vector.  ``lens``: a host sequence, or an int32 device vector (then nothing waits on the host).  Runs
+        on the CURRENT stream (the phase that calls it: ``synthesize_batch`` queues it on the bulk stream behind the decoder) and
+        does not synchronise; the scratch comes from this engine's workspace pool, one buffer per (B, T), which that stream owns.
+        ``token2sv`` stays the per-voice path that makes ``sv_ref``; the two agree to fp32 rounding, not bit for bit."""
+        if tokens_btq.dim() != 3 or int(tokens_btq.shape[2]) != self.Q or tokens_btq.is_floating_point():
+            raise ValueError(f"tokens_btq must be integer codes [B, T, {self.Q}], got {tuple(tokens_btq.shape)}")
+        B, T = int(tokens_btq.shape[0]), int(tokens_btq.shape[1])
+        if B == 0:
+            raise ValueError("speaker_vectors: at least one row")
+        if T == 0:
+            return torch.zeros(B, int(self.cfg.sv_student_dim), device=self.device)
+        tok = tokens_btq.to(self.device)
+        if tok.dtype != torch.int32:
+            tok = tok.to(torch.int32)
+        if tok.stride(2) != 1 or (T > 1 and tok.stride(1) != self.Q):
+            tok = tok.contiguous()
+        ws = self.ws.get("spk.ws", (int(hip.load().sopro_spk_workspace_bytes(self.eng.h, B, T)) // 4,), torch.int32)
+        return hip.spk_embed_rows(self.eng, tok, lens, ws=ws)
+
     # ------------------------------------------------------------------ per-utterance conditioning
     @torch.inference_mode()
     def prepare_conditioning(self, text_ids_1d: torch.Tensor, ref: PreparedReference, *, max_frames: int,

@@ -58,6 +58,9 @@ class EngineHandle:
         hip._check(lib.sopro_engine_create(C.byref(cfg), C.byref(h)), "sopro_engine_create")
         self.h = h
         self._keep = []
+        # widths of the speaker vector and of the Token2SV encoder (hip.spk_embed_rows sizes its outputs from them)
+        self.sv_dim = int(cfg.sv_student_dim)
+        self.spk_width = int(tensors["token2sv.emb"].shape[1]) if "token2sv.emb" in tensors else None
         for name, t in tensors.items():
             if not (t.is_cuda and t.dtype in (torch.float32, torch.int32) and 1 <= t.dim() <= 4):
                 continue

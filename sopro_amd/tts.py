@@ -146,18 +146,23 @@ class SoproTTS:
                    temperature: float = 1.05, anti_loop: bool = True, style_strength: Optional[float] = None,
                    ref_seconds: Optional[float] = None, min_gen_frames: Optional[int] = None,
                    seed: Optional[int] = None, speed: float = 1.0, pitch: float = 0.0, watermark=None,
-                   silence=None, denoise=None, report: Optional[list] = None, crop=None, formant: Optional[float] = None) -> torch.Tensor:
+                   silence=None, denoise=None, report: Optional[list] = None, crop=None, formant: Optional[float] = None,
+                   similarity: Optional[list] = None) -> torch.Tensor:
         """reference: src/sopro/model.py:531-575 -> waveform [1, 1, N] on ``self.device``.  ``seed`` (new) pins the sampler's
         draws: the same seed, text and voice give the same audio; without it every call is a new take (the reference
         draws from torch's global generator; its CLI seeds that once, src/sopro/cli.py:72-75).  ``speed``, ``pitch``, ``formant``,
         ``silence``, ``watermark`` (new): applied to the decoded waveform, see ``sopro_amd.effects``; at their defaults nothing is launched.
         ``denoise``, ``report`` (new): the input side, forwarded to ``prepare_reference``; with ``ref`` or ``ref_tokens_tq`` there is
         no waveform to clean and ``denoise`` other than None is refused.  ``crop`` (new): which ``ref_seconds`` of the recording are
-        encoded, forwarded likewise and refused likewise."""
+        encoded, forwarded likewise and refused likewise.  ``similarity`` (new): a sink like ``report`` - a list passed in receives
+        one ``VoiceMatch``, the generated tokens' speaker vector against ``ref.sv_ref`` (see ``synthesize_batch``); ``None``: nothing
+        is launched."""
         from . import crop as CR
         from . import denoise as D
         from . import effects
+        from . import voicematch as VM
 
+        VM.sink_of(similarity, "synthesize")
         fx = effects.Effects.of(speed, pitch, silence, watermark, formant)
         D.refuse_without_waveform(denoise, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
         CR.refuse_without_waveform(crop, "synthesize", ref=ref, ref_tokens_tq=ref_tokens_tq)
@@ -170,6 +175,9 @@ class SoproTTS:
             style_strength=float(style_strength if style_strength is not None else self.cfg.style_strength),
             min_gen_frames=min_gen_frames, seed=seed)
         wav = self.codec.decode_full(tokens)
+        if similarity is not None:
+            with self.model.on_stream(bulk=True):
+                similarity[:] = self._voice_matches(tokens.unsqueeze(0), [int(tokens.shape[0])], [ref])
         if wav.numel() == 0:
             return wav
         return effects.apply(wav.reshape(1, -1), [int(wav.shape[-1])], [fx])[0].reshape(1, 1, -1)
@@ -183,7 +191,8 @@ class SoproTTS:
                          row_ids: Optional[Sequence[int]] = None, padded: bool = False,
                          speed: Union[float, Sequence[float]] = 1.0, alignment: Optional[list] = None,
                          align_heads=None, pitch: Union[float, Sequence[float]] = 0.0,
-                         watermark=None, silence=None, effects=None, formant=None) -> Union[List[torch.Tensor], "PaddedBatch"]:
+                         watermark=None, silence=None, effects=None, formant=None,
+                         similarity: Optional[list] = None) -> Union[List[torch.Tensor], "PaddedBatch"]:
         """New: B utterances in one pass (batched AR graph, NAR and Mimi decode) -> list of [1, 1, N_b].
         ``nonces`` / ``row_ids``: per-utterance sampler stream of a scheduler that coalesces requests (see model._ARRun).
         ``padded`` (opt-in, the long-form join's input): return the decoder's batch as it is instead of per-row slices - a
@@ -197,11 +206,20 @@ class SoproTTS:
         position path, frame range per position, confidence; in frames, before any stretch) by a post-pass on the bulk stream
         (``model.align_batch``: the AR stack replayed over the generated tokens, ``hip.align_scores`` / ``hip.align_paths``);
         ``align_heads``: the (layer, head) pairs whose attention is averaged (default all 12).  ``None``: nothing is launched.
-        ``effects`` (internal): the rows' ``effects.Effects`` as they are, instead of the five keywords."""
+        ``effects`` (internal): the rows' ``effects.Effects`` as they are, instead of the five keywords.
+        ``similarity``: a sink as well - a list passed in is filled with one ``VoiceMatch`` per row: the cosine between the speaker
+        vector of the row's generated tokens ([frames, Q], over the row's own length; ``model.speaker_vectors``, every row as its own
+        unpadded utterance) and that row's ``ref.sv_ref``, queued on the bulk stream behind the decoder (three launches for the
+        batch, fp32 in both precision modes); a row without frames gives ``VoiceMatch(0.0, 0)``.  It reads tokens only: the
+        waveforms are the same bits with and without it.  ``None``: nothing is launched and nothing is allocated.  What cosine
+        means "same speaker" is for the caller to calibrate (``sopro_amd.voicematch``)."""
         import contextlib
         import time
 
         from . import effects as E
+        from . import voicematch as VM
+
+        VM.sink_of(similarity, "synthesize_batch")
 
         ids = list(text_ids) if text_ids is not None else [self.encode_text(t) for t in texts]
         # (a bad value is refused before anything runs)
@@ -263,6 +281,8 @@ class SoproTTS:
             if max(lens) == 0:
                 if alignment is not None:
                     alignment[:] = self.model.align_batch(state["prep"], state, heads=align_heads)
+                if similarity is not None:
+                    similarity[:] = VM.matches([0.0] * B, [0] * B)
                 if padded:
                     return PaddedBatch(torch.zeros(B, 0, device=self.device), [0] * B, torch.zeros(B, 0, self.model.Q, dtype=torch.long, device=self.device), [0] * B)
                 return [torch.zeros(1, 1, 0, device=self.device) for _ in range(B)]
@@ -284,6 +304,8 @@ class SoproTTS:
                 timings["_bulk_t1"] = time.perf_counter()
             if alignment is not None:  # (queued behind the decoder on the bulk stream)
                 alignment[:] = self.model.align_batch(state["prep"], state, heads=align_heads)
+            if similarity is not None:  # (likewise; the tokens are the engine's own matrix, read before the next pass writes it)
+                similarity[:] = self._voice_matches(codes, lens, refs)
             hop = int(self.codec.mc.frame_samples)
             wav, n_samples, cuts = E.apply(wav, [n * hop for n in lens], fxs)
             toks = None
@@ -411,7 +433,8 @@ class SoproTTS:
         before the join, so ``parts`` are the finished rows, cue times refer to the audio as it is heard and the pauses the join puts
         between sentences are untouched by the squeeze; the pauses are divided by ``speed`` and not touched by ``pitch``.
         ``watermark``: the batches run unmarked and the joined waveform is marked in one launch, so the carrier's phase is continuous
-        across the segments (``parts`` stay unmarked).  Full parameter list:
+        across the segments (``parts`` stay unmarked).  ``voice_match=True`` also fills ``voice``: one ``VoiceMatch`` per entry of
+        ``segments`` (the segment's generated tokens against the voice's ``sv_ref``, see ``voice_similarity``).  Full parameter list:
         ``longform.synthesize_long`` (``denoise=``, ``crop=`` and ``report=`` among them: the input side, as in ``synthesize``)."""
         from .longform import synthesize_long
 
@@ -479,6 +502,93 @@ class SoproTTS:
         CR.refuse_without_window(crop, "voice_pitch", ref_seconds)
         x = self.codec.reference_waveform(ref_audio_path, crop_seconds=ref_seconds if ref_seconds > 0 else None, denoise=denoise, crop=crop)
         return self.pitch_track(x, params=params)
+
+    # ------------------------------------------------------------------ voice similarity (sopro_amd.voicematch)
+    def _voice_matches(self, tokens_btq: torch.Tensor, lens: Sequence[int], refs: Sequence[PreparedReference]) -> list:
+        """One ``VoiceMatch`` per row of a padded token batch against one reference per row, on the CURRENT stream (three launches
+        and one copy of B floats to the host, which waits for them)."""
+        from . import hip
+        from . import voicematch as VM
+
+        lens = [int(n) for n in lens]
+        if len(refs) != len(lens):
+            raise ValueError(f"one reference per row ({len(lens)}), got {len(refs)}")
+        if int(tokens_btq.shape[1]) == 0 or max(lens) == 0:
+            return VM.matches([0.0] * len(lens), [0] * len(lens))
+        sv = self.model.speaker_vectors(tokens_btq, lens)
+        if all(r is refs[0] for r in refs):
+            ref_m = refs[0].sv_ref.to(self.device, torch.float32).reshape(1, -1).expand(len(lens), -1).contiguous()
+        else:
+            ref_m = torch.cat([r.sv_ref.to(self.device, torch.float32).reshape(1, -1) for r in refs], dim=0).contiguous()
+        return VM.matches(hip.spk_cosine(sv, ref_m).tolist(), lens)
+
+    def _voice_rows(self, what: str, wav, tokens, lens):
+        """``wav=`` (one 24 kHz clip, encoded by ``codec.encode_waveform``) or ``tokens=`` (+ ``lens=``) -> (tokens [B, T, Q], lens on
+        the host, batched)."""
+        from . import voicematch as VM
+
+        if (wav is None) == (tokens is None):
+            raise ValueError(f"{what} wants wav=... or tokens=... (one of them)")
+        if tokens is not None:
+            return VM.token_rows(tokens, lens, self.model.Q)
+        if lens is not None:
+            raise ValueError(f"{what}: lens= goes with tokens=")
+        if not isinstance(wav, torch.Tensor) or not wav.is_floating_point() or wav.numel() == 0 or wav.numel() != int(wav.shape[-1]):
+            raise ValueError(f"{what}: wav must be one floating-point clip [N], [1, N] or [1, 1, N] with N >= 1 (24 kHz)")
+        codes = self.codec.encode_waveform(wav.reshape(-1))
+        return codes.unsqueeze(0), [int(codes.shape[0])], False
+
+    @torch.inference_mode()
+    def speaker_vectors(self, *, tokens: Optional[torch.Tensor] = None, lens=None, wav: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """New: unit speaker vectors -> fp32 [B, sv_student_dim] on the device (a row without frames: zeros).  ``tokens``: codec tokens
+        [T, Q] or a padded batch [B, T, Q] with ``lens`` (valid frames per row; default T); or ``wav``: one 24 kHz clip ([N] / [1, N] /
+        [1, 1, N], what ``synthesize`` returns), encoded by the Mimi encoder first.  Every row is the model's Token2SV of its own
+        frames as an unpadded utterance - what ``encode_speaker`` gives for them one voice at a time - in two launches for the whole
+        batch on the bulk stream, which is synchronised before the call returns.  fp32 in both precision modes."""
+        t, lens_h, _ = self._voice_rows("speaker_vectors", wav, tokens, lens)
+        with self.model.on_stream(bulk=True):
+            sv = self.model.speaker_vectors(t, lens_h)
+        self.model.bulk_stream.synchronize()
+        return sv
+
+    @torch.inference_mode()
+    def voice_similarity(self, *, ref, wav: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, lens=None):
+        """New: did this take keep the voice?  -> ``VoiceMatch(cosine, frames)``: the cosine between the clip's speaker vector and
+        ``ref.sv_ref``.  The clip is ``wav`` (one 24 kHz clip, encoded first) or ``tokens`` [T, Q]; a padded batch ``tokens`` [B, T, Q]
+        with ``lens`` gives a list, one ``VoiceMatch`` per row, against ``ref`` (one ``PreparedReference`` for every row, or a
+        sequence with one per row).  Runs on the bulk stream and waits for the result.  There is no threshold here: what cosine
+        means "same speaker" depends on the checkpoint (``sopro_amd.voicematch``)."""
+        t, lens_h, batched = self._voice_rows("voice_similarity", wav, tokens, lens)
+        refs = list(ref) if isinstance(ref, (list, tuple)) else [ref] * len(lens_h)
+        if not all(isinstance(r, PreparedReference) for r in refs):
+            raise TypeError("voice_similarity(ref=...) wants a PreparedReference (or one per row)")
+        with self.model.on_stream(bulk=True):
+            out = self._voice_matches(t, lens_h, refs)
+        return out if batched else out[0]
+
+    @torch.inference_mode()
+    def identify_voice(self, *, voices, wav: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, top: int = 5) -> list:
+        """New: which of my stored voices is this clip?  -> the ``top`` best ``VoiceHit(index, name, cosine)``, best first (equal
+        cosines: the lower index first).  ``voices``: a ``VoiceBank`` (build it once and keep it) or a sequence of
+        ``PreparedReference``; the clip is ``wav`` (one 24 kHz clip) or ``tokens`` [T, Q].  One Token2SV pass and one bank cosine
+        launch on the bulk stream; the ranking is done on the host.  No threshold: the best hit of a clip whose voice is not in the
+        bank is still a hit."""
+        from . import hip
+        from . import voicematch as VM
+
+        top = VM.check_top(top)
+        bank = VM.as_bank(voices)
+        t, lens_h, batched = self._voice_rows("identify_voice", wav, tokens, None)
+        if batched:
+            raise ValueError("identify_voice: one clip at a time (tokens [T, Q])")
+        if bank.dim != int(self.cfg.sv_student_dim):
+            raise ValueError(f"identify_voice: the bank's vectors have {bank.dim} elements, this model's {int(self.cfg.sv_student_dim)}")
+        if lens_h[0] == 0:
+            raise ValueError("identify_voice: the clip has no frames")
+        with self.model.on_stream(bulk=True):
+            sv = self.model.speaker_vectors(t, lens_h)
+            cos = hip.spk_cosine(sv, bank.on(self.device), bank=True)[0].tolist()
+        return VM.rank(cos, bank.names, top)
 
     def save_wav(self, path: str, wav: torch.Tensor) -> None:
         """reference: src/sopro/model.py:582-583 (16-bit PCM via the stdlib; soundfile is not required)."""
